@@ -6,17 +6,20 @@ LeastAllocated + BalancedAllocation (synthetic cluster).  A step
 pods run through the scheduleOne loop (filter -> score -> selectHost -> assume, every pod in queue
 order) on the device-resident snapshot; K steps x pods-per-step = the config's 10,000 pods.
 
-Prints ONE JSON line (rank 0) with pods/s, node-evals/s, the roofline of the dominant kernel
-(k_batch / k_tbatch, timed with HIP events on the engine's stream) and the CPU baseline (the C
-restatement of the reference algorithm, oracle/c, timed on this host's cores on a bounded sample).
-At N=1 the line carries `extra` records timed in the same run, each with its own roofline, PMC
-traffic and CPU baseline: (b) at 100k nodes, the topology configs (c) and (d) at 5k and 100k nodes
-(BASELINE.json: "at 5k & 100k nodes") and one 125k-node GPU's worth of config (e).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints
+pods/s, node-evals/s and ms_per_step; --dump-outputs DIR also writes what the last timed step
+returned (the kgpu_result fields, DIR/<field>.npy).  Everything else is behind --full: the roofline
+of the dominant kernel (k_batch / k_tbatch, timed with HIP events on the engine's stream in a pass
+of its own), the per-cycle latency, the compile / drop-in / extender cycles and the CPU baseline
+(the C restatement of the reference algorithm, oracle/c, timed on the host's cores on a bounded
+sample).  With --full at N=1 the line carries `extra` records timed in the same run (at most --extra-steps steps each), each with its
+own roofline, PMC traffic and CPU baseline: (b) at 100k nodes, the topology configs (c) and (d) at
+5k and 100k nodes (BASELINE.json: "at 5k & 100k nodes") and one 125k-node GPU's worth of config (e).
 
 N > 1: the default workload is config (e), the 1M-node cluster of 8 x 125k-node
-shards, with a config (b) record beside it.  Under torch.distributed.run the ranks come from the
-environment; `bench.py --gpus N` started bare spawns its N rank processes itself.  The line records
-how many ranks the RCCL communicator and the xGMI mailboxes actually held (`comm`).
+shards, with a config (b) record beside it under --full.  Under torch.distributed.run the ranks
+come from the environment; `bench.py --gpus N` started bare spawns its N rank processes itself.  The
+line records how many ranks the RCCL communicator and the xGMI mailboxes actually held (`comm`).
 """
 import argparse
 import json
@@ -62,17 +65,20 @@ def host_info():
     return {"nproc": os.cpu_count() or 1, "affinity_cpus": min(aff, share) if share > 0 else aff, "cpu_model": model}
 
 
-def make_workload(cfg, n_nodes, n_pods, shard=None):
+def make_workload(cfg, n_nodes, n_pods, shard=None, head=None):
     """(nodes, existing pods, init pods, measured pods, profile, compiled).  Init pods (config a: the
     scheduler_perf initPods, performance-config.yaml:1-13) are scheduled before the timed region.
     Config (e) comes straight from the columnar generator (cluster.sharded_spread_compiled, pinned
     equal to the object path by tests/test_cluster_fast.py): nodes is None and `compiled` holds this
-    rank's shard of the compiled snapshot; every other config returns compiled=None."""
+    rank's shard of the compiled snapshot; every other config returns compiled=None.  head: config (b)
+    builds only that many pods of the head of the queue (config_b_queries compiles the whole queue)."""
     from kgpu import cluster, native
     if cfg == "e":  # (b)+(c), zone = i % 64: --nodes is the shard per GPU (1M over 8 GPUs: --nodes 125000)
         rng = None if shard is None else native.shard_range(n_nodes, shard[1], shard[0])
         comp, compiled, pods, prof = cluster.sharded_spread_compiled(n_nodes=n_nodes, n_pods=n_pods, shard=rng)
         return None, [], [], pods, prof, (comp, compiled)
+    if cfg == "b" and head is not None:
+        n_pods = min(n_pods, head)
     return _object_workload(cfg, n_nodes, n_pods) + (None,)
 
 
@@ -93,6 +99,27 @@ def _object_workload(cfg, n_nodes, n_pods):
     raise SystemExit("config %r not benchmarked yet" % cfg)
 
 
+def config_b_queries(fw, pods, n_nodes, n_pods):
+    """Config (b)'s n_pods compiled queries when only the head of the queue (`pods`) exists as
+    objects, so that set-up does not grow by the marshalling of 1000 pod objects per step.  A config
+    (b) query is a function of the pod's requests but for its uid, the pod's 1-based place in the
+    queue: the head and one pod per distinct pair of requests are compiled in one call (one set of
+    pools), every query is its pair's row, and the head must come out as the compiler made it.
+    tests/test_bench_cli.py holds the whole queue to the object path.  (queries, pools, pools as arrays)."""
+    import numpy as np
+    from kgpu import cluster
+    cpu, mem = cluster.fit_least_balanced_requests(n_nodes, n_pods)
+    _, first, inv = np.unique(cpu * (1 << 20) + mem, return_index=True, return_inverse=True)
+    reps = [cluster.pod("p%d" % i, "%dm" % cpu[i], "%dMi" % mem[i]) if cpu[i] else cluster.pod("p%d" % i)
+            for i in first]
+    q_c, pc, pnp, errs = fw.compile_pods(pods + reps)
+    assert not errs, errs
+    q = q_c[len(pods):][inv.reshape(-1)]
+    q["uid"] = np.arange(1, n_pods + 1)
+    assert q[:len(pods)].tobytes() == q_c[:len(pods)].tobytes(), "config (b): a query is not its requests' row"
+    return q, pc, pnp
+
+
 def pmc_traffic(cfg, n_local, launch_pods, kname):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes of this
     exact workload (the newest profiles/r*_pmc_traffic.json holding it; tools/pmc_summary.py), or None."""
@@ -107,9 +134,20 @@ def pmc_traffic(cfg, n_local, launch_pods, kname):
     return None
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the kgpu_result records the last timed step returned to its caller (one per pod
+    of the step, in queue order), one float64 array per field: <out_dir>/<field>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name in res.dtype.names:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(res[name]).astype(np.float64))
+
+
 def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latency_pods, rank, world, local,
-            dist_on, cpu_thread_counts=None):
-    """One workload: K timed steps of B pods after W warmup steps.  Returns the JSON record (rank 0)."""
+            dist_on, cpu_thread_counts=None, full=True, dump_dir=None):
+    """One workload: K timed steps of B pods after W warmup steps.  Returns the JSON record (rank 0).
+    full=False stops after the timed steps: the record then ends at `placed` (no kernel timing pass,
+    roofline, latency, compile / drop-in / extender cycles or CPU baseline)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -124,7 +162,9 @@ def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latenc
     n_cluster = n_nodes_per_gpu * world
     sharded = dist_on or args.shard
     shard = (rank, world) if sharded else None
-    nodes, existing, init, pods, prof, compiled = make_workload(cfg, n_cluster, n_pods, shard=shard)
+    # the pods that anything below reads as objects: compile_costs' 1000, the drop-in's, the extender's
+    head = max(1000, args.dropin_pods, args.extender_pods)
+    nodes, existing, init, pods, prof, compiled = make_workload(cfg, n_cluster, n_pods, shard=shard, head=head)
     fw = GpuFramework(prof, nodes, existing, pods_hint=init[:16] + pods[:16], device=local, shard=shard,
                       compiled=compiled)
     comm = None
@@ -142,11 +182,14 @@ def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latenc
             dist.all_reduce(lo, op=dist.ReduceOp.MIN)
             comm.update({"min_rccl_nranks_over_ranks": int(lo[0]), "min_xgmi_nranks_over_ranks": int(lo[1]),
                          "min_xgmi_peers_mapped_over_ranks": int(lo[2])})
-    q_all, pc, pnp, errs = fw.compile_pods(init + pods)
-    assert not errs, errs
+    if len(pods) < n_pods:
+        q_all, pc, pnp = config_b_queries(fw, pods, n_cluster, n_pods)
+    else:
+        q_all, pc, pnp, errs = fw.compile_pods(init + pods)
+        assert not errs, errs
     q_init, q = q_all[:len(init)], q_all[len(init):]
     log("workload %s: %d nodes (%d on this rank), %d pods, compiled in %.1fs"
-        % (cfg, n_cluster, fw.snap.n_nodes, len(pods), time.time() - t_gen))
+        % (cfg, n_cluster, fw.snap.n_nodes, n_pods, time.time() - t_gen))
     eng = fw.engine
     if args.no_persistent:
         eng.set_option(abi.OPT_PERSISTENT, 0)
@@ -236,6 +279,26 @@ def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latenc
     res_all = np.concatenate(results)
     placed = int((res_all["node"] >= 0).sum())
     pods_per_s = n_pods / elapsed
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, results[-1])
+    head = {
+        "metric": "pods scheduled/sec", "value": round(pods_per_s, 2), "unit": "pods/s", "n_gpus": world,
+        "steps": K, "warmup": W, "ms_per_step": round(1e3 * elapsed / K, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+        "config": {"workload": "(%s) %d nodes / %d pods" % (cfg, n_cluster, n_pods), "profile": PROFILES[cfg],
+                   "nodes": n_cluster, "nodes_per_gpu": fw.snap.n_nodes, "pods": n_pods, "pods_per_step": B,
+                   "percentage_of_nodes_to_score": 100,
+                   "parallelism": ("node shards x%d, %s" % (world, "granules through xGMI peer stores (persistent kernel)"
+                                                              if xgmi else "RCCL all-gather per pod"))
+                   if sharded else "1 GPU"},
+        "series": "%s:%d" % (cfg, n_nodes_per_gpu),
+        "node_evals_per_s": round(pods_per_s * n_cluster, 1),
+        "comm": comm,
+        "placed": placed,
+    }
+    if not full:
+        eng.close()
+        return head
 
     # kernel timing pass (separate: per-launch events perturb the timed loop)
     if dist_on:
@@ -328,20 +391,7 @@ def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latenc
             cpu["pods_by_threads"] = samples
 
     traffic = pmc_traffic(cfg, n_local, launch_pods, kname)
-    rec = {
-        "metric": "pods scheduled/sec", "value": round(pods_per_s, 2), "unit": "pods/s", "n_gpus": world,
-        "steps": K, "warmup": W, "ms_per_step": round(1e3 * elapsed / K, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-        "config": {"workload": "(%s) %d nodes / %d pods" % (cfg, n_cluster, n_pods), "profile": PROFILES[cfg],
-                   "nodes": n_cluster, "nodes_per_gpu": fw.snap.n_nodes, "pods": n_pods, "pods_per_step": B,
-                   "percentage_of_nodes_to_score": 100,
-                   "parallelism": ("node shards x%d, %s" % (world, "granules through xGMI peer stores (persistent kernel)"
-                                                              if xgmi else "RCCL all-gather per pod"))
-                   if sharded else "1 GPU"},
-        "series": "%s:%d" % (cfg, n_nodes_per_gpu),
-        "node_evals_per_s": round(pods_per_s * n_cluster, 1),
-        "comm": comm,
-        "placed": placed,
+    rec = dict(head, **{
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                      "kernel": kname,
@@ -355,7 +405,7 @@ def measure(args, cfg, n_nodes_per_gpu, B, K, W, cpu_sample, cpu_threads, latenc
         "compile": comp_rec,
         "dropin": dropin_rec,
         "extender": ext_rec,
-    }
+    })
     # release the device context before the next workload and before interpreter teardown (under
     # rocprofv3 the HIP runtime may be finalized before a garbage-collected engine would be)
     eng.close()
@@ -525,13 +575,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the kernel "
+                         "timing pass and roofline, kgpu_schedule_one latency, the compile / drop-in / extender "
+                         "cycles, the CPU baseline and the --extras records (the options below that size them "
+                         "have no effect without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the kgpu_result fields of the last timed step (node, feasible, evaluated, scored, "
+                         "score; one entry per pod of the step) to DIR/<field>.npy as float64")
     ap.add_argument("--config", default=None,
                     help="workload (BASELINE.json configs a-e); default (b) on one GPU, (e) on N > 1")
     ap.add_argument("--nodes", type=int, default=None,
                     help="nodes per GPU; default 5000, and 125000 for (e) (1M nodes over 8 GPUs)")
     ap.add_argument("--pods-per-step", type=int, default=1000)
-    ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="pods timed for the CPU baseline (-1: the whole workload, 0: skip)")
+    ap.add_argument("--cpu-sample", type=int, default=20000,
+                    help="pods timed for the CPU baseline, at most the workload's (-1: the whole workload, 0: skip)")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--latency-pods", type=int, default=200, help="pods timed one at a time through kgpu_schedule_one")
     ap.add_argument("--dropin-pods", type=int, default=200,
@@ -554,6 +612,9 @@ def main():
                          "%s on one GPU (BASELINE.json's metric is quoted at 5k and 100k nodes for configs b-d), %s "
                          "on N > 1; '' for none" % (DEFAULT_EXTRAS_1GPU, DEFAULT_EXTRAS_NGPU))
     ap.add_argument("--extra-cpu-sample", type=int, default=1000, help="pods of each extra record's CPU baseline")
+    ap.add_argument("--extra-steps", type=int, default=20,
+                    help="timed steps of each extra record, at most --steps (a long headline run does not "
+                         "lengthen the extra workloads)")
     ap.add_argument("--reset-at-exit", action="store_true", help="hipDeviceReset() before exiting (profiling runs)")
     ap.add_argument("--batch-helper", type=int, default=None,
                     help="KGPU_OPT_BATCH_HELPER (default: the library's, 1 = config (b)'s helper wave)")
@@ -601,15 +662,17 @@ def main():
     extras = parse_extras(args.extras if args.extras is not None else
                           ("" if args.config else (DEFAULT_EXTRAS_NGPU if world > 1 else DEFAULT_EXTRAS_1GPU)))
     line = measure(args, cfg, n_nodes, args.pods_per_step, args.steps, args.warmup, args.cpu_sample,
-                   args.cpu_threads, args.latency_pods, rank, world, local, dist_on)
+                   args.cpu_threads, args.latency_pods, rank, world, local, dist_on, full=args.full,
+                   dump_dir=args.dump_outputs)
     line["launcher"] = os.environ.get("KGPU_BENCH_LAUNCHER", "external (torch.distributed.run)" if dist_on else "none")
     recs = []
     for xcfg, xn in extras:
-        if args.shard or (xcfg, xn) == (cfg, n_nodes):
+        if not args.full or args.shard or (xcfg, xn) == (cfg, n_nodes):
             continue
         # each record: its own roofline and a CPU baseline over extra_cpu_sample pods, at 1 and 16
         # workers (the reference's parallelize.Until width) up to 10k nodes, at 16 above
-        recs.append(measure(args, xcfg, xn, args.pods_per_step, args.steps, args.warmup, args.extra_cpu_sample,
+        recs.append(measure(args, xcfg, xn, args.pods_per_step, min(args.steps, args.extra_steps), args.warmup,
+                            args.extra_cpu_sample,
                             args.cpu_threads, args.latency_pods, rank, world, local, dist_on,
                             cpu_thread_counts=sorted({1, 4, 8, args.cpu_threads} if xn <= 10000 else
                                                      {1, 8, args.cpu_threads})))
@@ -630,7 +693,8 @@ def main():
                 "one_p50_p99": [lt.get("p50_us"), lt.get("p99_us")] if lt else None,
                 "compile_us": r.get("compile_us_per_pod"), "dropin_pods_s": di.get("pods_s"),
                 "extender_pods_s": ex.get("pods_s")}
-    line["summary"] = [brief(r) for r in [line] + recs]
+    if args.full:
+        line["summary"] = [brief(r) for r in [line] + recs]
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist_on:

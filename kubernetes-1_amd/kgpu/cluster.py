@@ -96,6 +96,25 @@ def fit_least_balanced(n_nodes=5000, n_pods=10000, seed=CLUSTER_SEED, zones=0):
     return nodes, [], pods, prof
 
 
+def fit_least_balanced_requests(n_nodes=5000, n_pods=10000, seed=CLUSTER_SEED):
+    """The requests of fit_least_balanced(n_nodes, n_pods)'s pods without building the pods: (cpu in
+    millicores, memory in Mi) per pod, 0 / 0 for a pod without requests.  The nodes take two draws
+    each; a pod takes one draw (no requests) or three, so where a pod's draws begin follows from the
+    pods before it (tests/test_cluster_fast.py pins the equality with the object path)."""
+    import numpy as np
+    d = _splitmix_draws(seed, 2 * n_nodes, 3 * n_pods)
+    bare = ((d % np.uint64(10)) < 1).tolist()
+    at, p = [0] * n_pods, 0
+    for i in range(n_pods):
+        at[i] = p
+        p += 1 if bare[p] else 3
+    at = np.array(at, np.int64)
+    none = np.array(bare, bool)[at]
+    cpu = 100 * (1 + (d[at + 1 - none] % np.uint64(40)).astype(np.int64))
+    mem = 128 * (1 + (d[at + 2 - 2 * none] % np.uint64(64)).astype(np.int64))
+    return np.where(none, 0, cpu), np.where(none, 0, mem)
+
+
 # ----------------------------------------------------------------------------- (c)
 def taints_affinity_spread(n_nodes=5000, n_pods=10000, seed=CLUSTER_SEED, n_zones=10, spread=True):
     """Config (c): taints (10% dedicated=infra:NoSchedule, 20% spot=true:PreferNoSchedule),

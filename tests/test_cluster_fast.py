@@ -64,3 +64,15 @@ def test_fast_generator_million_nodes_is_quick():
     assert arrays["label_val"].shape == (2, 125000)
     assert int(arrays["label_val"][1][0]) == 375000
     assert len(order) == 1_000_000
+
+
+@pytest.mark.parametrize("n_nodes,n_pods", [(1, 1), (7, 40), (300, 2500), (5000, 3)])
+def test_config_b_requests_match_object_pods(n_nodes, n_pods):
+    """cluster.fit_least_balanced_requests against the pods fit_least_balanced builds."""
+    _, _, pods, _ = cluster.fit_least_balanced(n_nodes=n_nodes, n_pods=n_pods)
+    cpu, mem = cluster.fit_least_balanced_requests(n_nodes, n_pods)
+    assert cpu.shape == mem.shape == (n_pods,)
+    want = [p["spec"]["containers"][0]["resources"].get("requests", {}) for p in pods]
+    got = [{"cpu": "%dm" % c, "memory": "%dMi" % m} if c else {} for c, m in zip(cpu.tolist(), mem.tolist())]
+    assert got == want
+    assert n_pods < 40 or ({} in want and any(want))  # both kinds of pod in the larger queues

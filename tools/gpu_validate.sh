@@ -12,7 +12,7 @@ cd $R && export TMPDIR=/tmp
 step() { local name=$1; shift; "$@" > $O/$name.log 2>&1; local rc=$?; echo "$name rc=$rc" >> $O/status.txt; return $rc; }
 step pytest timeout -k 10 1000 python -u -m pytest $SEL -x -v -m gpu --timeout 300 --timeout-method thread || exit 1
 step smoke timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit 1
-step bench timeout -k 10 700 python -u bench.py --steps 20 --warmup 5 || exit 1
+step bench timeout -k 10 700 python -u bench.py --full --steps 20 --warmup 5 || exit 1
 export KGPU_HOST_TRACE=1
 for w in b:5000 c:5000 d:5000 b:100000 c:100000 d:100000; do
   cfg=${w%%:*}; n=${w##*:}
