@@ -635,7 +635,8 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
 #define KGPU_OPT_COOPERATIVE 10
 /* KGPU_OPT_BATCH_GEO (11): the smallest k_batch geometry considered (index into the geometry table
  * of kgpu_kernels.hip: 0 = 64 row threads, 1 = 128, 2 = 192, 3 = 448, 4 = 960, 5 = 512 x 4 rows per
- * lane); the first one whose workgroups fit the GPU is used.  Default 0. */
+ * lane, 6 = 512 x 8 rows per lane, streamed from the node columns: up to 1,048,320 nodes per GPU); the
+ * first one whose workgroups fit the GPU is used.  Values 0-6 (clamped).  Default 0. */
 #define KGPU_OPT_BATCH_GEO 11
 /* KGPU_OPT_ARENA_BYTES (12): bytes a short cycle (kgpu_schedule_one, batches of up to 64 pods) may
  * stage beside its DevState and queries for its single host-to-device copy (changed pools, topology
@@ -656,8 +657,10 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * and key travel; 0 = every pod's rows are evaluated after the previous pod's assume. */
 #define KGPU_OPT_TOPO_AHEAD 15
 /* KGPU_OPT_TBATCH_GEO (16): the smallest persistent topology kernel geometry considered (0 = 256
- * threads x 1 row per lane, 1 = 512 x 1, 2 = 512 x 2); the first whose workgroups fit the GPU is used.
- * Default 1 (256 x 1 measured equal at 5k nodes, with twice the exchange traffic). */
+ * threads x 1 row per lane, 1 = 512 x 1, 2 = 512 x 2, 3 = 512 x 4, 4 = 512 x 8; 3 and 4 stream their
+ * rows from the node columns: up to 1,048,576 nodes per GPU); the first whose workgroups fit the GPU is
+ * used.  Values 0-4 (clamped).  Default 1 (256 x 1 measured equal at 5k nodes, with twice the exchange
+ * traffic). */
 #define KGPU_OPT_TBATCH_GEO 16
 /* KGPU_OPT_HOLD_GROUP (17): test hook -- on an ordinary (non-cooperative) persistent launch, workgroup
  * `value` leaves at once, as a workgroup that never became resident (-1, the default: none). */
@@ -689,6 +692,14 @@ int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
  * for the first time, kgpu_prepare_pods); out[4] = whole pod-table uploads (the table is otherwise sent
  * incrementally).  Returns how many counters exist. */
 int kgpu_debug_counters(const kgpu_ctx* ctx, int64_t* out, int32_t n);
+/* Pure host, no context: the geometry the engine would pick.  kernel 1 = k_batch, 2 = k_tbatch;
+ * first = KGPU_OPT_*_GEO value.  Returns the geometry index (>= 0) and fills out[0..3] = threads per
+ * workgroup (row threads), rows per lane, workgroups, nodes per workgroup; KGPU_E_CAPACITY if none. */
+int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]);
+/* The last kgpu_schedule_* call's last persistent launch: out[0] = 0 none (reset at the start of every
+ * call, so a fall-back to per-pod launches shows), 1 k_batch, 2 k_tbatch; out[1] geometry index;
+ * out[2..5] as kgpu_geometry_for's out[0..3]. */
+int kgpu_debug_geometry(const kgpu_ctx* ctx, int32_t out[6]);
 /* Diagnostics of KGPU_OPT_TOPO_RESIDENT: out[0] = persistent topology runs that started from the
  * resident state, out[1] = runs that recomputed it. */
 int kgpu_debug_topo_resident(const kgpu_ctx* ctx, int64_t out[2]);

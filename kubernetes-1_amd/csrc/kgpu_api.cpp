@@ -275,6 +275,7 @@ struct kgpu_ctx {
   int64_t n_coop_retry = 0, n_persist = 0, n_coop = 0;  // kgpu_debug_counters
   int64_t n_class_init = 0, n_pod_table_full = 0;       // ... k_class_init launches, whole pod-table uploads
   int state_launches = 0;           // launches of the current call that may change device state
+  int32_t last_geo[6] = {0, -1, 0, 0, 0, 0};  // kgpu_debug_geometry: the call's last persistent launch
   // pipelined batches (kgpu_schedule_batch_submit / _wait): two slots, each with its pinned staging block,
   // device block (DevState | queries | run pointers | abort word), granules and pinned result records
   struct PipeSlot {
@@ -365,6 +366,18 @@ int on_exception(kgpu_ctx* c, bool invalidate) noexcept {
     }
   }
   return code;
+}
+
+// kgpu_debug_geometry: a persistent launch of the current kgpu_schedule_* call
+void note_geometry(kgpu_ctx* c, int kernel, int geo, int groups, int per) {
+  int threads = 0, rows = 0;
+  kgpu::geometry_shape(kernel, geo, &threads, &rows);
+  const int32_t v[6] = {kernel, geo, threads, rows, groups, per};
+  std::copy(v, v + 6, c->last_geo);
+}
+void reset_geometry(kgpu_ctx* c) {
+  const int32_t v[6] = {0, -1, 0, 0, 0, 0};
+  std::copy(v, v + 6, c->last_geo);
 }
 
 #define HIP_OK(c, x)                                                                           \
@@ -1796,6 +1809,7 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   ++c->n_persist;
   c->n_coop += coop ? 1 : 0;
   ++c->state_launches;
+  note_geometry(c, 2, geo, groups, per);
   if (kgpu::launch_tbatch(dst, a, groups, geo, c->spec, xg, coop, c->stream))
     return fail(c, KGPU_E_DEVICE, std::string("k_tbatch launch failed: ") + hipGetErrorString(hipGetLastError()));
   if (c->ar.on) ht(c, 7);  // 7: the launch (API call)
@@ -2198,7 +2212,8 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   if (timed) HIP_OK(c, hipEventRecord(t0, c->stream));
   size_t ev = 2;
   int64_t timed_passes = 0;
-  // Persistent geometry: one workgroup per CU at most, K node rows per lane in registers.
+  // Persistent geometry: one workgroup per CU at most, K node rows per lane (in registers up to K = 4,
+  // streamed from the node columns at K = 8).
   int per = 0, groups = 0;
   const bool xg = c->xg_nranks > 1 && c->xgmi;  // persistent runs exchange granules over xGMI
   const bool sharded = c->comm != nullptr || xg;
@@ -2439,6 +2454,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       ++c->n_persist;
       c->n_coop += coop ? 1 : 0;
       ++c->state_launches;
+      note_geometry(c, 1, kidx, groups, per);
       if (kgpu::launch_batch(dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
         return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
       if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
@@ -3415,6 +3431,7 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   *reinterpret_cast<int32_t*>(static_cast<char*>(ps.res) + sizeof(kgpu_result) * (size_t)n) = -1;
   const bool timed = stats != nullptr;
   if (timed) HIP_OK(c, hipEventRecord(ps.t0, c->stream));
+  note_geometry(c, 1, kidx, groups, per);
   if (kgpu::launch_batch(reinterpret_cast<const DevState*>(d), ba, groups, kidx, c->spec, coop, c->batch_helper,
                          c->stream))
     return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
@@ -3784,6 +3801,30 @@ int kgpu_debug_counters(const kgpu_ctx* c, int64_t* out, int32_t n) {
   return 5;
 }
 
+int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]) try {
+  if ((kernel != 1 && kernel != 2) || n_nodes < 0 || max_groups < 1 || !out) return KGPU_E_INVAL;
+  int per = 0, groups = 0;
+  const int geo = kernel == 1 ? kgpu::batch_geometry(n_nodes, std::min(max_groups, 256), &per, &groups, first)
+                              : kgpu::tbatch_geometry(n_nodes, std::min(max_groups, 256), &per, &groups, first);
+  int threads = 0, rows = 0;
+  if (geo < 0 || !kgpu::geometry_shape(kernel, geo, &threads, &rows)) return KGPU_E_CAPACITY;
+  out[0] = threads;
+  out[1] = rows;
+  out[2] = groups;
+  out[3] = per;
+  return geo;
+} catch (...) {
+  return on_exception(nullptr, false);
+}
+
+int kgpu_debug_geometry(const kgpu_ctx* c, int32_t out[6]) try {
+  if (!c || !out) return KGPU_E_INVAL;
+  for (int i = 0; i < 6; ++i) out[i] = c->last_geo[i];
+  return KGPU_OK;
+} catch (...) {
+  return on_exception(nullptr, false);
+}
+
 int kgpu_debug_topo_resident(const kgpu_ctx* c, int64_t out[2]) {
   if (!c || !out) return KGPU_E_INVAL;
   out[0] = (int64_t)c->tc_hits;
@@ -3821,10 +3862,10 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_TOPO_FUSED) c->topo_fused = value != 0;
   else if (option == KGPU_OPT_TOPO_PERSISTENT) c->tfast = value != 0;
   else if (option == KGPU_OPT_COOPERATIVE) c->coop = value != 0;
-  else if (option == KGPU_OPT_BATCH_GEO) c->batch_geo_first = (int)std::max<int64_t>(0, value);
+  else if (option == KGPU_OPT_BATCH_GEO) c->batch_geo_first = (int)std::min<int64_t>(std::max<int64_t>(0, value), 6);
   else if (option == KGPU_OPT_BATCH_HELPER) c->batch_helper = value != 0;
   else if (option == KGPU_OPT_TOPO_AHEAD) c->topo_ahead = value != 0;
-  else if (option == KGPU_OPT_TBATCH_GEO) c->tbatch_geo_first = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2);
+  else if (option == KGPU_OPT_TBATCH_GEO) c->tbatch_geo_first = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4);
   else if (option == KGPU_OPT_TOPO_RESIDENT) {
     c->tc_on = value != 0;
     c->tc.valid = false;
@@ -4021,6 +4062,7 @@ int kgpu_schedule_batch(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const 
   }
   if (!c || (n > 0 && (!qs || !results))) return KGPU_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return KGPU_E_DEVICE;
+  reset_geometry(c);
   return run_batch(c, qs, n, pools, first_seq, results, stats, false, 1);
 } catch (...) {
   return on_exception(c, true);
@@ -4034,6 +4076,7 @@ int kgpu_schedule_batch_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n,
     if (rs_) return rs_;
   }
   if (hipSetDevice(c->device) != hipSuccess) return KGPU_E_DEVICE;
+  reset_geometry(c);
   return pipe_submit(c, qs, n, pools, first_seq, results, stats);
 } catch (...) {
   c->pipe_q.clear();
@@ -4058,6 +4101,7 @@ int kgpu_schedule_one(kgpu_ctx* c, const kgpu_pod_query* q, const kgpu_pools* po
   if (!c || !q || !res) return KGPU_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return KGPU_E_DEVICE;
   size_t before = c->recs.size();
+  reset_geometry(c);
   int rc = run_batch(c, q, 1, pools, pod_seq, res, nullptr, true, assume);
   if (rc) return rc;
   if (assumed_slot) *assumed_slot = c->recs.size() > before ? (int32_t)c->recs.size() - 1 : -1;

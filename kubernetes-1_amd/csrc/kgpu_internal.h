@@ -541,6 +541,9 @@ int launch_shard_pack(const DevState* st, int parity, int blocks, int what, void
 // variant-B spare), -1 when N does not fit in max_groups workgroups.
 // first: the smallest geometry index considered (KGPU_OPT_BATCH_GEO; 0 = all)
 int batch_geometry(int N, int max_groups, int* per, int* groups, int first = 0);
+// Row threads per workgroup and rows (slots) per lane of geometry index `geo` of the persistent kernel
+// (kernel 1 = k_batch, 2 = k_tbatch); false when there is no such geometry.
+bool geometry_shape(int kernel, int geo, int* threads, int* rows);
 // helper: config (b)'s profile on the one-row-wave geometry takes the helper-wave instantiation (HB)
 int launch_batch(const DevState* st, const BatchArgs& a, int groups, int kidx, int spec, bool coop, bool helper,
                  void* stream);

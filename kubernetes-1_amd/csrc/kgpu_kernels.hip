@@ -1202,7 +1202,8 @@ __global__ __launch_bounds__(kBlock) void k_shard_pack(const DevState* __restric
 
 // ---------------------------------------------------------------- persistent batch kernel
 // A run of pods in queue order inside ONE launch.  Workgroup g owns nodes [g*per, (g+1)*per) and
-// keeps their resource rows in registers for the whole run: K slots per row lane, per = K*B - 1
+// keeps their resource rows in registers for the whole run (up to K = 4; K = 8 loads each row from
+// the node columns where a pod evaluates it: kStream): K slots per row lane, per = K*B - 1
 // (the last slot of the last lane is the spare below).  Per pod every workgroup publishes one
 // 8-byte granule -- valid bit | ((score+1) << 40 | rank40), 0 key = no feasible node -- with a
 // write-through (sc1) store into the pod's row of slots, and every workgroup derives the same
@@ -1254,6 +1255,16 @@ __device__ __forceinline__ NodeRes lane_row(const NodeRes& r, int src) {
   t.ic = __builtin_bit_cast(double, lane64(__builtin_bit_cast(int64_t, r.ic), src));
   t.im = __builtin_bit_cast(double, lane64(__builtin_bit_cast(int64_t, r.im), src));
   return t;
+}
+
+// A node's row as the persistent kernels hold it: the resource columns and, for a profile whose
+// Least / MostAllocated divide by reciprocal, the reciprocals.  The streamed geometries (rows per lane
+// above what the register file holds) call it for every row of every pod; the resident ones once.
+template <bool RECIP>
+__device__ __forceinline__ NodeRes load_row(const DevState& st, int n) {
+  NodeRes r = load_res(st, n);
+  if constexpr (RECIP) set_recips(r);
+  return r;
 }
 
 // NodeInfo.AddPod on a register copy only (the variant-B row): resource columns and pod count.
@@ -1754,19 +1765,24 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
     return;
   }
 
-  // ---- row waves.  Rows stay in registers; assume_row writes every change through to the node
-  // columns as well.  The spare slot holds no node of its own.
-  NodeRes r[K];
+  // ---- row waves.  Up to four rows per lane stay in registers; assume_row writes every change through
+  // to the node columns as well.  The spare slot holds no node of its own.
+  // kStream (more than four rows per lane): eight rows are 176 registers of the 168 a lane of this
+  // block shape has, so no row is resident -- each is loaded from the node columns where a pod
+  // evaluates it.  The columns are exact: a row's only writer inside the run is the lane that owns it
+  // (assume_row), which is also its only reader.  r[0] is then the spare slot's row alone.
+  constexpr bool kStream = K > 4;
+  constexpr int KR = kStream ? 1 : K;
+  static_assert(!kStream || (W > 1 && !HB), "streamed rows: the candidate row travels through sh.brow");
+  // Allocatable never changes inside the run: LeastAllocated / MostAllocated divide through
+  // exact reciprocal-plus-remainder-correction division (ratio100)
+  constexpr bool kRecip = (SM & kDefRes) != 0 && SM != kRuntime;
+  NodeRes r[KR];
 #pragma unroll
-  for (int j = 0; j < K; ++j) {
+  for (int j = 0; j < KR; ++j) {
     const int n = lo + j * B + tid;
     r[j] = NodeRes{};
-    if (!spare_slot(j, K, tid, B) && n < st.N) {
-      r[j] = load_res(st, n);
-      // Allocatable never changes inside the run: LeastAllocated / MostAllocated divide through
-      // exact reciprocal-plus-remainder-correction division (ratio100)
-      if constexpr ((SM & kDefRes) != 0 && SM != kRuntime) set_recips(r[j]);
-    }
+    if (!kStream && !spare_slot(j, K, tid, B) && n < st.N) r[j] = load_row<kRecip>(st, n);
   }
   // The row loads complete here.  Left to the first use inside the pod loop, their wait would sit
   // in the loop body as a vmcnt(0) -- and vmcnt counts stores too, so every iteration would wait
@@ -1802,7 +1818,7 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
           t = sh.brow[(i - 1) & 1];
         }
         assume_regs(qp, t);
-        if (tid == B - 1) r[K - 1] = t;
+        if (tid == B - 1) r[KR - 1] = t;
       }
       if constexpr (HB) {
         // Fit and the tie-break rank here; Least and Balanced from the helper waves
@@ -1828,7 +1844,14 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
         for (int j = 0; j < K; ++j) {
           const bool spare = spare_slot(j, K, tid, B);
           const int n = spare ? lo + cand : lo + j * B + tid;
-          keys[j] = (spare ? fast_b : n < st.N) ? node_key<FM, SM>(st, q, r[j], n, tk) : 0;
+          if constexpr (kStream) {
+            const bool live = spare ? fast_b : n < st.N;
+            NodeRes rj = r[0];  // the spare slot's candidate row (lane B - 1, slot K - 1)
+            if (!spare && live) rj = load_row<kRecip>(st, n);
+            keys[j] = live ? node_key<FM, SM>(st, q, rj, n, tk) : 0;
+          } else {
+            keys[j] = (spare ? fast_b : n < st.N) ? node_key<FM, SM>(st, q, r[j], n, tk) : 0;
+          }
         }
       }
       KGPU_STAMP(i, 5);
@@ -1866,7 +1889,12 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
 #pragma unroll
       for (int j = 0; j < K; ++j)
         if (j == jb) {
-          assume_row(st, qp, r[j], lo + (j * B + tid));
+          if constexpr (kStream) {
+            NodeRes t = load_res(st, lo + (j * B + tid));
+            assume_row(st, qp, t, lo + (j * B + tid));
+          } else {
+            assume_row(st, qp, r[j], lo + (j * B + tid));
+          }
           assume_counts(st, pa.first + i - 1, lo + (j * B + tid));
         }
     }
@@ -1880,7 +1908,11 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
           const uint64_t tk = pod_tie_key(st.seed, pa.seq0 + i);
 #pragma unroll
           for (int j = 0; j < K; ++j)
-            if (j == jb) keys[j] = node_key<FM, SM>(st, q, r[j], lo + (j * B + tid), tk);
+            if (j == jb) {
+              // (streamed: this lane's own assume_row stores precede the load in program order)
+              if constexpr (kStream) keys[j] = node_key<FM, SM>(st, q, load_row<kRecip>(st, lo + (j * B + tid)), lo + (j * B + tid), tk);
+              else keys[j] = node_key<FM, SM>(st, q, r[j], lo + (j * B + tid), tk);
+            }
         }
         const Cand c = wave_recombine<K, B>(sh, p, keys);
         if (lane == 0) {
@@ -1897,7 +1929,10 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
         // stage pod i's candidate row (pod i-1 already assumed on it) for pod i+1's variant B
 #pragma unroll
         for (int j = 0; j < K; ++j)
-          if (j == cand / B) sh.brow[p] = r[j];
+          if (j == cand / B) {
+            if constexpr (kStream) sh.brow[p] = load_row<kRecip>(st, lo + cand);
+            else sh.brow[p] = r[j];
+          }
         if (i != pa.skip_release_at) lds_release(&sh.bready, i + 1);
       }
     }
@@ -3346,27 +3381,66 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     if (tid < ta.nranks) sh_ptx[tid] = ta.ptx[tid];
   }
   const int64_t txw = XG ? tx_row_words(ta.nranks) : 0;
-  NodeRes r[K];
-  TStatic sr[K];
-  TCnt cc[K];
+  // kStream (four or eight rows per lane): a row's resource words, static words and cached counts are
+  // 38 registers, so eight resident rows alone would take more than the 256 a lane has at two waves
+  // per SIMD.  No row is resident then: the pod loop loads each row's NodeRes and TStatic from the node
+  // columns where it evaluates the row (assume_row and the mcnt / tcnt increments write every change
+  // through, and a row's only writer inside the run is the lane that owns it), and keeps per-pod
+  // results only (feas, o, rk, the zone).
+  constexpr bool kStream = K >= 4;
+  constexpr int KR = kStream ? 1 : K;
+  NodeRes r[KR];
+  TStatic sr[KR];
+  TCnt cc[KR];
+  // kStream: the same words per row and pod -- the node's eligibility bits ...
+  auto load_em = [&](int n) -> uint64_t {
+    uint64_t em = 0;
+    for (int s0 = 0; s0 < ta.n_sigs; s0 += 8) {
+      uint32_t w[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        w[u] = s0 + u < ta.n_sigs ? gp(ta.elig)[cp(ta.sigs)[s0 + u].elig_word + (n >> 5)] : 0u;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) em |= (uint64_t)((w[u] >> (n & 31)) & 1u) << (s0 + u);
+    }
+    return em;
+  };
+  // ... and its other words that never change inside a run (TStatic)
+  auto load_static = [&](int n, uint64_t em) -> TStatic {
+    TStatic s{{0, 0}, {0, 0}, 0, -1, em};
+    s.unsched = gp(st.unsched)[n];
+    s.zone = gp(st.zone_id)[n];
+    // constant indices only: a dynamically indexed private array lives in scratch memory
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+      if (w >= st.TW) break;
+      s.tns[w] = gp(st.taint_nosched)[(size_t)w * st.N + n];
+      s.tpr[w] = gp(st.taint_prefer)[(size_t)w * st.N + n];
+    }
+    return s;
+  };
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const int n = lo + j * B + tid;
-    r[j] = NodeRes{};
-    sr[j] = TStatic{{0, 0}, {0, 0}, 0, -1, 0};
-    cc[j] = TCnt{{-1, -1}, {0, 0}};
-    if (n < st.N) {
-      // the node's eligibility bits (k_tbatch_init's bitmaps): one load per signature, all in flight
-      uint64_t em = 0;
-      for (int s0 = 0; s0 < ta.n_sigs; s0 += 8) {
-        uint32_t w[8];
+    if (!kStream || j == 0) {
+      r[kStream ? 0 : j] = NodeRes{};
+      sr[kStream ? 0 : j] = TStatic{{0, 0}, {0, 0}, 0, -1, 0};
+      cc[kStream ? 0 : j] = TCnt{{-1, -1}, {0, 0}};
+    }
+    if constexpr (!kStream) {
+      if (n < st.N) {
+        // the node's eligibility bits (k_tbatch_init's bitmaps): one load per signature, all in flight
+        uint64_t em = 0;
+        for (int s0 = 0; s0 < ta.n_sigs; s0 += 8) {
+          uint32_t w[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          w[u] = s0 + u < ta.n_sigs ? gp(ta.elig)[cp(ta.sigs)[s0 + u].elig_word + (n >> 5)] : 0u;
+          for (int u = 0; u < 8; ++u)
+            w[u] = s0 + u < ta.n_sigs ? gp(ta.elig)[cp(ta.sigs)[s0 + u].elig_word + (n >> 5)] : 0u;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) em |= (uint64_t)((w[u] >> (n & 31)) & 1u) << (s0 + u);
+          for (int u = 0; u < 8; ++u) em |= (uint64_t)((w[u] >> (n & 31)) & 1u) << (s0 + u);
+        }
+        sr[j].em = em;
       }
-      sr[j].em = em;
     }
     if (n < st.N) {
       if (ta.diag && !(K == 1 && SM != kRuntime)) {
@@ -3379,16 +3453,18 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
           gp(st.diag_norm)[(size_t)sc * st.N + n] = 0;
         }
       }
-      r[j] = load_res(st, n);
-      if constexpr (kDef) set_recips(r[j]);
-      sr[j].unsched = gp(st.unsched)[n];
-      sr[j].zone = gp(st.zone_id)[n];
-      // constant indices only: a dynamically indexed private array lives in scratch memory
+      if constexpr (!kStream) {
+        r[j] = load_res(st, n);
+        if constexpr (kDef) set_recips(r[j]);
+        sr[j].unsched = gp(st.unsched)[n];
+        sr[j].zone = gp(st.zone_id)[n];
+        // constant indices only: a dynamically indexed private array lives in scratch memory
 #pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        if (w >= st.TW) break;
-        sr[j].tns[w] = gp(st.taint_nosched)[(size_t)w * st.N + n];
-        sr[j].tpr[w] = gp(st.taint_prefer)[(size_t)w * st.N + n];
+        for (int w = 0; w < 2; ++w) {
+          if (w >= st.TW) break;
+          sr[j].tns[w] = gp(st.taint_nosched)[(size_t)w * st.N + n];
+          sr[j].tpr[w] = gp(st.taint_prefer)[(size_t)w * st.N + n];
+        }
       }
     }
   }
@@ -3473,14 +3549,27 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     // ---- Filter + raw scores of this workgroup's rows
     bool feas[K];
     TRow o[K];
+    int32_t zone[kStream ? K : 1];  // streamed rows: the row's zone, for the normalize pass
     uint32_t sf = 0, smaxT = 0, smaxNA = 0, snon = 0, sadjmin = 0xFFFFFFFFu, sadjmax = 0, sdmax = 0, szoned = 0;
     int64_t simin = INT64_MAX, simax = INT64_MIN;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const int n = lo + j * B + tid;
       feas[j] = false;
+      if constexpr (kStream) zone[j] = -1;
       if (n >= st.N) continue;
-      if (kAhead && ind_have) {
+      int zj = 0;
+      if constexpr (kStream) {
+        // the row from the node columns; its counts are read where the pod needs them (no cache)
+        const NodeRes rj = load_row<kDef>(st, n);
+        const TStatic sj = load_static(n, load_em(n));
+        TCnt cj{{-1, -1}, {0, 0}};
+        zone[j] = zj = sj.zone;
+        const uint32_t sw = trow_eval<FM, SM, kDef>(st, ta, q, tp, rj, n, H, PT, M, pany, aff_any, LAB, j * B + tid,
+                                                    sj, cj, o[j], ta.diag, (int64_t*)nullptr);
+        if (ta.diag) gp(st.status)[n] = sw;  // kgpu_schedule_one: the cycle's Filter verdicts
+        if (sw) continue;
+      } else if (kAhead && ind_have) {
         // the non-topology half was evaluated ahead; the topology half reads this pod's tables
         if (!ind_ok) continue;
         o[j] = ind_o;
@@ -3508,7 +3597,8 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
       simin = min(simin, o[j].ipa);
       simax = max(simax, o[j].ipa);
       sdmax = max(sdmax, (uint32_t)o[j].ds);
-      const int z = sr[j].zone;
+      int z = zj;
+      if constexpr (!kStream) z = sr[j].zone;
       if (z >= 0) {
         szoned = 1;
         if (o[j].ds && z < ta.zones) atomicAdd(ZSUM + z, o[j].ds);
@@ -3676,7 +3766,9 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
         if (tp.dpts_cls != -2) {
           double f = Mx;
           if (dmax_node > 0) f = Mx * ((double)(dmax_node - o[j].ds) / (double)dmax_node);
-          const int z = sr[j].zone;
+          int z;
+          if constexpr (kStream) z = zone[j];
+          else z = sr[j].zone;
           if (have_zones && z >= 0) {
             double zs = Mx;
             if (dmax_zone > 0) zs = Mx * ((double)(dmax_zone - S[kTFixed + ta.soft_words + z]) / (double)dmax_zone);
@@ -3916,12 +4008,19 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
 #pragma unroll
         for (int j = 0; j < K; ++j)
           if (local == j * B + tid) {
-            assume_row(st, q, r[j], wl);
+            if constexpr (kStream) {
+              NodeRes t = load_res(st, wl);
+              assume_row(st, q, t, wl);
+            } else {
+              assume_row(st, q, r[j], wl);
+            }
             for (int a = 0; a < tp.assume_cls.count; ++a) {
               const int col = cp(ta.aux)[tp.assume_cls.begin + a];
               gp(st.mcnt)[(size_t)col * st.N + wl] += 1;
-              cc[j].v[0] += cc[j].col[0] == col ? 1 : 0;
-              cc[j].v[1] += cc[j].col[1] == col ? 1 : 0;
+              if constexpr (!kStream) {
+                cc[j].v[0] += cc[j].col[0] == col ? 1 : 0;
+                cc[j].v[1] += cc[j].col[1] == col ? 1 : 0;
+              }
             }
             for (int a = 0; a < tp.own_tcls.count; ++a)
               gp(st.tcnt)[(size_t)cp(ta.aux)[tp.own_tcls.begin + a] * st.N + wl] += 1;
@@ -4058,18 +4157,21 @@ constexpr uint32_t kAutoscalerSM = (kProviderSM & ~bit(KGPU_S_LEAST_ALLOCATED)) 
 struct TGeo {
   int B, K;
 };
-// 512 threads x 1 or 2 rows per lane (two waves per SIMD, no VGPR spills): up to 262,144 nodes per
-// GPU in 256 workgroups; larger shards take the per-pod topology launches.
+// 512 threads x 1 or 2 rows per lane with every row in registers (two waves per SIMD, no VGPR
+// spills): up to 262,144 nodes per GPU in 256 workgroups.  512 x 4 and 512 x 8 stream their rows from
+// the node columns (k_tbatch kStream): up to 1,048,576 nodes per GPU; only a larger shard takes the
+// per-pod topology launches.
 // 256 x 1: one wave per SIMD, up to 65,536 nodes per GPU (KGPU_OPT_TBATCH_GEO 0; it measured equal
 // to 512 x 1 at 5k nodes -- the per-pod phases are latency chains, not issue-bound -- so the default
 // starts at 512 x 1).
-constexpr TGeo kTGeo[] = {{256, 1}, {512, 1}, {512, 2}};
-constexpr int kNumTGeo = 3;
+constexpr TGeo kTGeo[] = {{256, 1}, {512, 1}, {512, 2}, {512, 4}, {512, 8}};
+constexpr int kNumTGeo = sizeof(kTGeo) / sizeof(kTGeo[0]);
 using TBatchFn = void (*)(const DevState*, TBatchArgs);
 template <uint32_t FM, uint32_t SM, bool kDef, bool XG>
 struct TBatchRow {
   static constexpr TBatchFn fn[kNumTGeo] = {k_tbatch<256, 1, FM, SM, kDef, XG>, k_tbatch<512, 1, FM, SM, kDef, XG>,
-                                            k_tbatch<512, 2, FM, SM, kDef, XG>};
+                                            k_tbatch<512, 2, FM, SM, kDef, XG>, k_tbatch<512, 4, FM, SM, kDef, XG>,
+                                            k_tbatch<512, 8, FM, SM, kDef, XG>};
 };
 // rows: 0 generic, 1 generic with Least/Most over {cpu:1, memory:1}, 2 default provider,
 // 3 ClusterAutoscaler provider; [1]: the node-sharded (xGMI) instantiations
@@ -4189,13 +4291,14 @@ int select_spec(const int32_t* filters, int nf, const int32_t* scores, int ns, b
 
 // Persistent geometries: (threads per workgroup, rows per lane).  256 x 1 keeps small clusters
 // on few workgroups; 1024 x 1 gives 4 waves per SIMD; 512 x 4 holds up to 524,288 nodes per GPU
-// (256 workgroups x 2048 rows) with every row in registers and no spills.  Larger shards take the
-// one-launch-per-pod path.
+// (256 workgroups x 2048 rows) with every row in registers and no spills; 512 x 8 streams its rows
+// from the node columns (k_batch kStream) and holds up to 1,048,320 nodes per GPU (256 x 4095).
+// Only a larger shard takes the one-launch-per-pod path.
 struct Geo {
   int B, K;
 };
-constexpr Geo kGeo[] = {{64, 1}, {128, 1}, {192, 1}, {448, 1}, {960, 1}, {512, 4}};  // B row threads (+ one communication wave), K slots per lane
-constexpr int kNumGeo = 6;
+constexpr Geo kGeo[] = {{64, 1}, {128, 1}, {192, 1}, {448, 1}, {960, 1}, {512, 4}, {512, 8}};  // B row threads (+ one communication wave), K slots per lane
+constexpr int kNumGeo = sizeof(kGeo) / sizeof(kGeo[0]);
 constexpr int kBatchLdsPad = 96 * 1024;
 
 template <uint32_t FM, uint32_t SM>
@@ -4203,10 +4306,12 @@ struct BatchRow {
   using Fn = void (*)(const DevState*, BatchArgs);
   static constexpr Fn fn[kNumGeo] = {k_batch<FM, SM, 1, 64, false>,  k_batch<FM, SM, 1, 128, false>,
                                      k_batch<FM, SM, 1, 192, false>, k_batch<FM, SM, 1, 448, false>,
-                                     k_batch<FM, SM, 1, 960, false>, k_batch<FM, SM, 4, 512, false>};
+                                     k_batch<FM, SM, 1, 960, false>, k_batch<FM, SM, 4, 512, false>,
+                                     k_batch<FM, SM, 8, 512, false>};
   static constexpr Fn xfn[kNumGeo] = {k_batch<FM, SM, 1, 64, true>,  k_batch<FM, SM, 1, 128, true>,
                                       k_batch<FM, SM, 1, 192, true>, k_batch<FM, SM, 1, 448, true>,
-                                      k_batch<FM, SM, 1, 960, true>, k_batch<FM, SM, 4, 512, true>};
+                                      k_batch<FM, SM, 1, 960, true>, k_batch<FM, SM, 4, 512, true>,
+                                      k_batch<FM, SM, 8, 512, true>};
 };
 using BatchFn = void (*)(const DevState*, BatchArgs);
 // the helper-wave instantiation (HB) of config (b)'s profile on the one-row-wave geometry
@@ -4249,6 +4354,20 @@ int batch_geometry(int N, int max_groups, int* per, int* groups, int first) {
     }
   }
   return -1;
+}
+
+bool geometry_shape(int kernel, int geo, int* threads, int* rows) {
+  if (kernel == 1 && geo >= 0 && geo < kNumGeo) {
+    *threads = kGeo[geo].B;
+    *rows = kGeo[geo].K;
+    return true;
+  }
+  if (kernel == 2 && geo >= 0 && geo < kNumTGeo) {
+    *threads = kTGeo[geo].B;
+    *rows = kTGeo[geo].K;
+    return true;
+  }
+  return false;
 }
 
 int launch_batch(const DevState* st, const BatchArgs& a, int groups, int geo, int spec, bool coop, bool helper,

@@ -24,7 +24,8 @@ EXPORTS = ["kgpu_abi_version", "kgpu_struct_sizes", "kgpu_create", "kgpu_destroy
            "kgpu_debug_fail_alloc", "kgpu_debug_pts_state", "kgpu_debug_ipa_state", "kgpu_debug_broken_linear",
            "kgpu_debug_wg_trace", "kgpu_debug_topo_resident",
            "kgpu_next_slot", "kgpu_adopt_pod", "kgpu_prepare_pods", "kgpu_filter_reasons", "kgpu_debug_counters",
-           "kgpu_schedule_batch_submit", "kgpu_schedule_batch_wait", "kgpu_pipelined"]
+           "kgpu_schedule_batch_submit", "kgpu_schedule_batch_wait", "kgpu_pipelined",
+           "kgpu_geometry_for", "kgpu_debug_geometry"]
 
 
 class KgpuError(RuntimeError):
@@ -82,6 +83,8 @@ def lib():
     L.kgpu_schedule_batch_submit.argtypes = [vp, vp, i32, C.POINTER(abi.Pools), i64, vp, vp]
     L.kgpu_schedule_batch_wait.argtypes = [vp]
     L.kgpu_pipelined.argtypes = [vp]
+    L.kgpu_geometry_for.argtypes = [i32, i32, i32, i32, vp]
+    L.kgpu_debug_geometry.argtypes = [vp, vp]
     L.kgpu_filter_reasons.argtypes = [vp, C.POINTER(abi.ReasonArgs), vp, i64, C.POINTER(i64)]
     if L.kgpu_abi_version() != abi.ABI_VERSION:
         raise KgpuError(abi.E_STATE, "ABI version mismatch")
@@ -100,6 +103,26 @@ def check_layout(L=None):
         bad = [(n, w, g) for (n, w), g in zip(abi.STRUCT_SIZES, got) if w != g]
         raise KgpuError(abi.E_STATE, "struct layout mismatch (python, C): %r" % bad)
     return True
+
+
+KERNEL_BATCH, KERNEL_TBATCH = 1, 2  # kgpu_geometry_for / kgpu_debug_geometry kernel ids
+_GEO_KERNELS = {0: None, KERNEL_BATCH: "k_batch", KERNEL_TBATCH: "k_tbatch"}
+
+
+def geometry_for(kernel, n_nodes, max_groups, first=None):
+    """kgpu_geometry_for: the persistent geometry the engine would pick for `n_nodes` nodes on at most
+    `max_groups` workgroups (pure host code: no context, no GPU).  kernel: KERNEL_BATCH (k_batch) or
+    KERNEL_TBATCH (k_tbatch); first: the OPT_BATCH_GEO / OPT_TBATCH_GEO value (None: that option's
+    default).  Returns {index, threads, rows_per_lane, groups, per}; KgpuError(E_CAPACITY) when no
+    geometry holds the cluster."""
+    if first is None:
+        first = 1 if kernel == KERNEL_TBATCH else 0
+    out = np.zeros(4, np.int32)
+    rc = lib().kgpu_geometry_for(kernel, n_nodes, max_groups, first, out.ctypes.data)
+    if rc < 0:
+        raise KgpuError(rc, "kgpu_geometry_for(%d, %d, %d, %d)" % (kernel, n_nodes, max_groups, first))
+    return {"index": rc, "threads": int(out[0]), "rows_per_lane": int(out[1]), "groups": int(out[2]),
+            "per": int(out[3])}
 
 
 class Engine:
@@ -318,6 +341,15 @@ class Engine:
         out = np.zeros(2, np.int64)
         self._check(lib().kgpu_debug_topo_resident(self.h, out.ctypes.data))
         return int(out[0]), int(out[1])
+
+    def geometry(self):
+        """kgpu_debug_geometry: the last schedule call's last persistent launch as {kernel, index,
+        threads, rows_per_lane, groups, per}; kernel is None when the call launched no persistent
+        kernel (every pod took per-pod launches), else "k_batch" or "k_tbatch"."""
+        out = np.zeros(6, np.int32)
+        self._check(lib().kgpu_debug_geometry(self.h, out.ctypes.data))
+        return {"kernel": _GEO_KERNELS[int(out[0])], "index": int(out[1]), "threads": int(out[2]),
+                "rows_per_lane": int(out[3]), "groups": int(out[4]), "per": int(out[5])}
 
     def counters(self):
         """kgpu_debug_counters: {coop_retries, persistent_launches, coop_launches, class_inits,
