@@ -700,6 +700,13 @@ int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32
  * call, so a fall-back to per-pod launches shows), 1 k_batch, 2 k_tbatch; out[1] geometry index;
  * out[2..5] as kgpu_geometry_for's out[0..3]. */
 int kgpu_debug_geometry(const kgpu_ctx* ctx, int32_t out[6]);
+/* Which instantiation the last kgpu_schedule_* call's last persistent launch ran (reset with
+ * kgpu_debug_geometry's record): out[0] = the profile row the launcher indexed (k_batch: the profile
+ * instantiation 0..3, 0 = the runtime profile; k_tbatch: 0 runtime, 1 runtime with default resources,
+ * 2 default, 3 autoscaler; -1 no persistent launch); out[1] = 1 for the node-sharded (xGMI)
+ * instantiation; out[2] = 1 for the helper-wave instantiation; out[3] = pods of the call that ran inside
+ * persistent launches, summed over its runs (the rest took per-pod launches). */
+int kgpu_debug_instantiation(const kgpu_ctx* ctx, int32_t out[4]);
 /* Diagnostics of KGPU_OPT_TOPO_RESIDENT: out[0] = persistent topology runs that started from the
  * resident state, out[1] = runs that recomputed it. */
 int kgpu_debug_topo_resident(const kgpu_ctx* ctx, int64_t out[2]);

@@ -276,6 +276,7 @@ struct kgpu_ctx {
   int64_t n_class_init = 0, n_pod_table_full = 0;       // ... k_class_init launches, whole pod-table uploads
   int state_launches = 0;           // launches of the current call that may change device state
   int32_t last_geo[6] = {0, -1, 0, 0, 0, 0};  // kgpu_debug_geometry: the call's last persistent launch
+  int32_t last_inst[4] = {-1, 0, 0, 0};       // kgpu_debug_instantiation: its profile row, xGMI, helper; pods so far
   // pipelined batches (kgpu_schedule_batch_submit / _wait): two slots, each with its pinned staging block,
   // device block (DevState | queries | run pointers | abort word), granules and pinned result records
   struct PipeSlot {
@@ -375,9 +376,18 @@ void note_geometry(kgpu_ctx* c, int kernel, int geo, int groups, int per) {
   const int32_t v[6] = {kernel, geo, threads, rows, groups, per};
   std::copy(v, v + 6, c->last_geo);
 }
+// kgpu_debug_instantiation: the same launch's profile row and flags, and its pods added to the call's sum
+void note_instantiation(kgpu_ctx* c, int row, bool xg, bool helper, int pods) {
+  c->last_inst[0] = row;
+  c->last_inst[1] = xg ? 1 : 0;
+  c->last_inst[2] = helper ? 1 : 0;
+  c->last_inst[3] += pods;
+}
 void reset_geometry(kgpu_ctx* c) {
   const int32_t v[6] = {0, -1, 0, 0, 0, 0};
   std::copy(v, v + 6, c->last_geo);
+  const int32_t w[4] = {-1, 0, 0, 0};
+  std::copy(w, w + 4, c->last_inst);
 }
 
 #define HIP_OK(c, x)                                                                           \
@@ -1810,6 +1820,7 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   c->n_coop += coop ? 1 : 0;
   ++c->state_launches;
   note_geometry(c, 2, geo, groups, per);
+  note_instantiation(c, kgpu::tbatch_row(c->spec, a.def_res != 0), xg, false, count);
   if (kgpu::launch_tbatch(dst, a, groups, geo, c->spec, xg, coop, c->stream))
     return fail(c, KGPU_E_DEVICE, std::string("k_tbatch launch failed: ") + hipGetErrorString(hipGetLastError()));
   if (c->ar.on) ht(c, 7);  // 7: the launch (API call)
@@ -2455,6 +2466,8 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       c->n_coop += coop ? 1 : 0;
       ++c->state_launches;
       note_geometry(c, 1, kidx, groups, per);
+      note_instantiation(c, kgpu::batch_row(c->spec), ba.R > 0,
+                         kgpu::batch_helper_used(c->spec, kidx, ba.R > 0, c->batch_helper), cnt);
       if (kgpu::launch_batch(dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
         return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
       if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
@@ -3275,11 +3288,13 @@ int assume_via_delta(kgpu_ctx* c, const kgpu_pod_query& q, const kgpu_pools* poo
 int run_batch(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_pools* pools, int64_t first_seq,
               kgpu_result* results, kgpu_stats* stats, bool diag, int32_t assume) {
   c->state_launches = 0;
+  const int32_t pods_before = c->last_inst[3];  // of the API call's earlier runs (a per-pod sequence nests here)
   int rc = run_batch_once(c, qs, n, pools, first_seq, results, stats, diag, assume);
   if (rc != kCleanAbort) return rc;
   ++c->n_coop_retry;
   c->force_coop = true;
   c->state_launches = 0;
+  c->last_inst[3] = pods_before;  // the aborted issue's pods are counted by the second issue alone
   rc = run_batch_once(c, qs, n, pools, first_seq, results, stats, diag, assume);
   c->force_coop = false;
   if (rc == kCleanAbort) {  // unreachable: a forced cooperative call never reports a clean abort
@@ -3432,6 +3447,7 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   const bool timed = stats != nullptr;
   if (timed) HIP_OK(c, hipEventRecord(ps.t0, c->stream));
   note_geometry(c, 1, kidx, groups, per);
+  note_instantiation(c, kgpu::batch_row(c->spec), false, kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper), n);
   if (kgpu::launch_batch(reinterpret_cast<const DevState*>(d), ba, groups, kidx, c->spec, coop, c->batch_helper,
                          c->stream))
     return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
@@ -3820,6 +3836,14 @@ int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32
 int kgpu_debug_geometry(const kgpu_ctx* c, int32_t out[6]) try {
   if (!c || !out) return KGPU_E_INVAL;
   for (int i = 0; i < 6; ++i) out[i] = c->last_geo[i];
+  return KGPU_OK;
+} catch (...) {
+  return on_exception(nullptr, false);
+}
+
+int kgpu_debug_instantiation(const kgpu_ctx* c, int32_t out[4]) try {
+  if (!c || !out) return KGPU_E_INVAL;
+  for (int i = 0; i < 4; ++i) out[i] = c->last_inst[i];
   return KGPU_OK;
 } catch (...) {
   return on_exception(nullptr, false);

@@ -547,6 +547,10 @@ bool geometry_shape(int kernel, int geo, int* threads, int* rows);
 // helper: config (b)'s profile on the one-row-wave geometry takes the helper-wave instantiation (HB)
 int launch_batch(const DevState* st, const BatchArgs& a, int groups, int kidx, int spec, bool coop, bool helper,
                  void* stream);
+// What launch_batch indexes (kgpu_debug_instantiation): the profile row for `spec`, and whether the
+// launch takes the helper-wave instantiation (sharded: BatchArgs.R > 0).
+int batch_row(int spec);
+bool batch_helper_used(int spec, int geo, bool sharded, bool helper);
 // Topology pipeline for one pod (PodArgs.pod): domain histograms, critical-path minima, filters,
 // scores, normalize + argmax, resolve + assume.  next_scratch: words of the next topology pod's
 // scratch to zero in the resolve launch (0 none).
@@ -580,6 +584,8 @@ int64_t kernel_layout_sig();
 int launch_tbatch_init(const DevState* st, const TBatchArgs& a, int groups, void* stream);
 int launch_tbatch(const DevState* st, const TBatchArgs& a, int groups, int geo, int spec, bool xg, bool coop,
                   void* stream);
+// The k_tbatch profile row launch_tbatch indexes for `spec` and TBatchArgs.def_res (kgpu_debug_instantiation).
+int tbatch_row(int spec, bool def_res);
 
 // ---------------------------------------------------------------- delta stream (kgpu_apply_delta)
 enum DeltaKind { kDAddPod = 0, kDRemovePod = 1, kDSetNode = 2 };

@@ -4229,12 +4229,14 @@ int launch_tbatch_init(const DevState* st, const TBatchArgs& a, int groups, void
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int tbatch_row(int spec, bool def_res) { return spec == 2 ? 2 : (spec == 3 ? 3 : (def_res ? 1 : 0)); }
+
 // spec: the k_eval profile instantiation (select_spec), def_res from the TBatchArgs
 int launch_tbatch(const DevState* st, const TBatchArgs& a, int groups, int geo, int spec, bool xg, bool coop,
                   void* stream) {
   if (geo < 0 || geo >= kNumTGeo) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int row = spec == 2 ? 2 : (spec == 3 ? 3 : (a.def_res ? 1 : 0));
+  const int row = tbatch_row(spec, a.def_res != 0);
   const TBatchFn fn = kTBatch[xg ? 1 : 0][row][geo];
   static bool attr[2][4][kNumTGeo] = {};
   if (!attr[xg ? 1 : 0][row][geo]) {
@@ -4370,14 +4372,20 @@ bool geometry_shape(int kernel, int geo, int* threads, int* rows) {
   return false;
 }
 
+int batch_row(int spec) { return spec < 0 || spec >= kNumSpecs ? 0 : spec; }
+
+bool batch_helper_used(int spec, int geo, bool sharded, bool helper) {
+  return helper && !sharded && geo == 0 && kBatchHelper[batch_row(spec)] != nullptr;
+}
+
 int launch_batch(const DevState* st, const BatchArgs& a, int groups, int geo, int spec, bool coop, bool helper,
                  void* stream) {
-  if (spec < 0 || spec >= kNumSpecs) spec = 0;
+  spec = batch_row(spec);
   if (geo < 0 || geo >= kNumGeo) return -1;
   // One workgroup per CU: a dynamic LDS reservation above half a CU's 160 KB keeps the dispatcher
   // from stacking two persistent workgroups on one CU (they would share its SIMDs).
   const int x = a.R > 0 ? 1 : 0;  // node-sharded over xGMI mailboxes
-  const bool hb = helper && !x && geo == 0 && kBatchHelper[spec] != nullptr;
+  const bool hb = batch_helper_used(spec, geo, x != 0, helper);
   const BatchFn fn = hb ? kBatchHelper[spec] : (x ? kBatchX : kBatch)[spec][geo];
   const int threads = kGeo[geo].B + 64 + (hb ? 2 * kGeo[geo].B : 0);
   static bool attr_set[3][kNumSpecs][kNumGeo] = {};

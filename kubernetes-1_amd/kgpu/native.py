@@ -25,7 +25,7 @@ EXPORTS = ["kgpu_abi_version", "kgpu_struct_sizes", "kgpu_create", "kgpu_destroy
            "kgpu_debug_wg_trace", "kgpu_debug_topo_resident",
            "kgpu_next_slot", "kgpu_adopt_pod", "kgpu_prepare_pods", "kgpu_filter_reasons", "kgpu_debug_counters",
            "kgpu_schedule_batch_submit", "kgpu_schedule_batch_wait", "kgpu_pipelined",
-           "kgpu_geometry_for", "kgpu_debug_geometry"]
+           "kgpu_geometry_for", "kgpu_debug_geometry", "kgpu_debug_instantiation"]
 
 
 class KgpuError(RuntimeError):
@@ -85,6 +85,7 @@ def lib():
     L.kgpu_pipelined.argtypes = [vp]
     L.kgpu_geometry_for.argtypes = [i32, i32, i32, i32, vp]
     L.kgpu_debug_geometry.argtypes = [vp, vp]
+    L.kgpu_debug_instantiation.argtypes = [vp, vp]
     L.kgpu_filter_reasons.argtypes = [vp, C.POINTER(abi.ReasonArgs), vp, i64, C.POINTER(i64)]
     if L.kgpu_abi_version() != abi.ABI_VERSION:
         raise KgpuError(abi.E_STATE, "ABI version mismatch")
@@ -350,6 +351,16 @@ class Engine:
         self._check(lib().kgpu_debug_geometry(self.h, out.ctypes.data))
         return {"kernel": _GEO_KERNELS[int(out[0])], "index": int(out[1]), "threads": int(out[2]),
                 "rows_per_lane": int(out[3]), "groups": int(out[4]), "per": int(out[5])}
+
+    def instantiation(self):
+        """kgpu_debug_instantiation: which instantiation the last schedule call's last persistent launch
+        ran, as {row, sharded, helper, persistent_pods}: row is the profile row the launcher indexed
+        (k_batch: 0 runtime, 1 fit, 2 default, 3 autoscaler; k_tbatch: 0 runtime, 1 runtime with default
+        resources, 2 default, 3 autoscaler; -1 when the call launched no persistent kernel);
+        persistent_pods counts the call's pods that ran inside persistent launches."""
+        out = np.zeros(4, np.int32)
+        self._check(lib().kgpu_debug_instantiation(self.h, out.ctypes.data))
+        return {"row": int(out[0]), "sharded": bool(out[1]), "helper": bool(out[2]), "persistent_pods": int(out[3])}
 
     def counters(self):
         """kgpu_debug_counters: {coop_retries, persistent_launches, coop_launches, class_inits,
