@@ -823,6 +823,40 @@ int kgpu_debug_ipa_state(kgpu_ctx* ctx, const kgpu_pod_query* q, const kgpu_pool
 int kgpu_debug_broken_linear(kgpu_ctx* ctx, const kgpu_shape_point* points, int32_t n_points, const int64_t* p,
                              int32_t n, int64_t* out);
 
+/* Diagnostic: one of the score arithmetic's device functions, the ones the kernels call, applied
+ * element-wise to n int64 operands a, b, c, d (all four arrays given; an op ignores the ones it does
+ * not name).  out[i] = the value, flag[i] = the `slow` flag of the reciprocal forms (1: the lane left
+ * the reciprocal path and, in LEAST_RECIP / MOST_RECIP, both resources were recomputed by the integer
+ * division), 0 for the other ops.  Reciprocals follow the persistent rows' rule (1/cap for
+ * 0 < cap < 2^52, else 0).  The caller keeps each op's precondition:
+ *   DIV_NONNEG   floor(a / b), 0 <= a, 0 < b
+ *   WDIV         Go's a / b (truncating), 0 < b
+ *   HALF         Go's a / 2
+ *   LEAST_ONE    leastRequestedScore(req b, cap a), exact form;  MOST_ONE likewise
+ *   LEAST_RECIP  the default LeastAllocated of cpu (cap a, req b) and memory (cap c, req d) as the
+ *                persistent rows compute it;  MOST_RECIP likewise
+ *   RATIO100     ratio100(x a, cap b): exact where flag = 0 (0 <= a <= 100 b, a < 2^52, 0 < b < 2^52),
+ *                unspecified where flag = 1
+ *   RATIO100_32  floor(a / b), 0 <= a <= 100 b < 2^31, 0 < b
+ *   BALANCED     balancedResourceScorer of cpu (cap a, req b) and memory (cap c, req d)
+ *   RTCR_ROUND   math.Round(float64(a) / float64(b)), 0 <= a, 0 < b, 2 a + b < 2^63 */
+enum {
+  KGPU_ARITH_DIV_NONNEG = 0,
+  KGPU_ARITH_WDIV = 1,
+  KGPU_ARITH_HALF = 2,
+  KGPU_ARITH_LEAST_ONE = 3,
+  KGPU_ARITH_MOST_ONE = 4,
+  KGPU_ARITH_LEAST_RECIP = 5,
+  KGPU_ARITH_MOST_RECIP = 6,
+  KGPU_ARITH_RATIO100 = 7,
+  KGPU_ARITH_RATIO100_32 = 8,
+  KGPU_ARITH_BALANCED = 9,
+  KGPU_ARITH_RTCR_ROUND = 10,
+  KGPU_ARITH_OPS = 11
+};
+int kgpu_debug_arith(kgpu_ctx* ctx, int32_t op, const int64_t* a, const int64_t* b, const int64_t* c,
+                     const int64_t* d, int64_t* out, int32_t* flag, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

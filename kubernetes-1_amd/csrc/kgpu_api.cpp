@@ -4525,6 +4525,36 @@ int kgpu_debug_broken_linear(kgpu_ctx* c, const kgpu_shape_point* points, int32_
   return on_exception(c, false);
 }
 
+int kgpu_debug_arith(kgpu_ctx* c, int32_t op, const int64_t* a, const int64_t* b, const int64_t* cc, const int64_t* d,
+                     int64_t* out, int32_t* flag, int32_t n) try {
+  if (c && !c->pipe_q.empty())
+    return fail(c, KGPU_E_STATE, "pipelined batches in flight: complete them with kgpu_schedule_batch_wait first");
+  if (c && c->unsettled) {  // a short cycle returned on its completion word: the stream first
+    const int rs_ = settle(c);
+    if (rs_) return rs_;
+  }
+  if (!c || !a || !b || !cc || !d || !out || !flag || op < 0 || op >= KGPU_ARITH_OPS || n <= 0 || n > (1 << 24))
+    return KGPU_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return KGPU_E_DEVICE;
+  fail_point();
+  const size_t N = (size_t)n;
+  int64_t* dv = nullptr;  // a, b, c, d, out (int64 each), then flag (int32)
+  HIP_OK(c, hipMalloc(&dv, sizeof(int64_t) * 5 * N + sizeof(int32_t) * N));
+  int32_t* df = reinterpret_cast<int32_t*>(dv + 5 * N);
+  const int64_t* in[4] = {a, b, cc, d};
+  bool ok = true;
+  for (int k = 0; k < 4 && ok; ++k)
+    ok = hipMemcpyAsync(dv + k * N, in[k], sizeof(int64_t) * N, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+  ok = ok && !kgpu::launch_debug_arith(op, dv, dv + N, dv + 2 * N, dv + 3 * N, dv + 4 * N, df, n, c->stream) &&
+       hipMemcpyAsync(out, dv + 4 * N, sizeof(int64_t) * N, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+       hipMemcpyAsync(flag, df, sizeof(int32_t) * N, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+       hipStreamSynchronize(c->stream) == hipSuccess;
+  (void)hipFree(dv);
+  return ok ? KGPU_OK : fail(c, KGPU_E_DEVICE, "arithmetic probe failed");
+} catch (...) {
+  return on_exception(c, false);
+}
+
 int kgpu_get_filter(kgpu_ctx* c, uint32_t* words) try {
   if (c && !c->pipe_q.empty())
     return fail(c, KGPU_E_STATE, "pipelined batches in flight: complete them with kgpu_schedule_batch_wait first");

@@ -567,6 +567,9 @@ inline int topo_barriers(int64_t min_values) { return min_values > 0 ? 5 : 4; }
 int launch_class_init(const DevState* st, int c0, int nc, int n_pods, void* stream);
 int launch_debug_broken_linear(const kgpu_shape_point* pts, int n_pts, const int64_t* p, int64_t* out, int n,
                                void* stream);
+// kgpu_debug_arith: op (KGPU_ARITH_*) over n elements of the device arrays a..d into out and flag
+int launch_debug_arith(int op, const int64_t* a, const int64_t* b, const int64_t* c, const int64_t* d, int64_t* out,
+                       int32_t* flag, int n, void* stream);
 int launch_topo_phase(const DevState* st, const PodArgs& a, int phase, int blocks, int64_t extra, void* stream);
 // Persistent topology run: signature bitmaps + pair registrations and histogram
 // initialization from the match-count columns (k_tbatch_init), then k_tbatch.  kidx: geometry.

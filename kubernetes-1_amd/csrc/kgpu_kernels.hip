@@ -327,18 +327,34 @@ __device__ __forceinline__ int64_t most_one(int64_t cap, int64_t req, double inv
 __device__ __forceinline__ int64_t wdiv(int64_t s, int64_t w) { return s >= 0 ? div_nonneg(s, w) : s / w; }
 __device__ __forceinline__ int64_t half(int64_t s) { return s >= 0 ? (s >> 1) : s / 2; }
 
+// The default resources (cpu and memory, weight 1 each) through the rows' reciprocals (nr.ic, nr.im:
+// set_recips, or 0 for the exact form): both quotients by ratio100, and both again by the integer
+// division when either lane fell outside ratio100's range (`slow`, reported for kgpu_debug_arith).
+__device__ __forceinline__ int64_t least_def(const NodeRes& nr, int64_t rc, int64_t rm, bool& slow) {
+  slow = false;
+  int64_t a = least_one(nr.ac, rc, nr.ic, slow), b = least_one(nr.am, rm, nr.im, slow);
+  if (slow) {
+    a = least_one(nr.ac, rc);
+    b = least_one(nr.am, rm);
+  }
+  return half(a + b);
+}
+__device__ __forceinline__ int64_t most_def(const NodeRes& nr, int64_t rc, int64_t rm, bool& slow) {
+  slow = false;
+  int64_t a = most_one(nr.ac, rc, nr.ic, slow), b = most_one(nr.am, rm, nr.im, slow);
+  if (slow) {
+    a = most_one(nr.ac, rc);
+    b = most_one(nr.am, rm);
+  }
+  return half(a + b);
+}
+
 template <bool kDef>
 __device__ __forceinline__ int64_t least_score(const DevState& st, const kgpu_pod_query& q, const NodeRes& nr,
                                                int n) {
   if constexpr (kDef) {
-    const int64_t rc = nr.zc + q.score_req[0], rm = nr.zm + q.score_req[1];
-    bool slow = false;
-    int64_t a = least_one(nr.ac, rc, nr.ic, slow), b = least_one(nr.am, rm, nr.im, slow);
-    if (slow) {
-      a = least_one(nr.ac, rc);
-      b = least_one(nr.am, rm);
-    }
-    return half(a + b);
+    bool slow;
+    return least_def(nr, nr.zc + q.score_req[0], nr.zm + q.score_req[1], slow);
   } else {
     int64_t s = 0;
     for (int i = 0; i < st.n_least; ++i) {
@@ -354,14 +370,8 @@ template <bool kDef>
 __device__ __forceinline__ int64_t most_score(const DevState& st, const kgpu_pod_query& q, const NodeRes& nr,
                                               int n) {
   if constexpr (kDef) {
-    const int64_t rc = nr.zc + q.score_req[0], rm = nr.zm + q.score_req[1];
-    bool slow = false;
-    int64_t a = most_one(nr.ac, rc, nr.ic, slow), b = most_one(nr.am, rm, nr.im, slow);
-    if (slow) {
-      a = most_one(nr.ac, rc);
-      b = most_one(nr.am, rm);
-    }
-    return half(a + b);
+    bool slow;
+    return most_def(nr, nr.zc + q.score_req[0], nr.zm + q.score_req[1], slow);
   } else {
     int64_t s = 0;
     for (int i = 0; i < st.n_most; ++i) {
@@ -398,6 +408,11 @@ __global__ void k_dbg_broken_linear(ShapeProbe s, const int64_t* __restrict__ p,
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = broken_linear(s.pts, s.n, p[i]);
 }
+// math.Round(float64(a) / float64(b)) for 0 <= a, 0 < b: a / b is never within an ulp of a .5
+// that it does not equal, so the exact half-away-from-zero integer rounding is the same value
+__device__ __forceinline__ int64_t rtcr_round(int64_t node_score, int64_t wsum) {
+  return (2 * node_score + wsum) / (2 * wsum);
+}
 __device__ __forceinline__ int64_t rtcr_score(const DevState& st, const kgpu_pod_query& q, const NodeRes& nr, int n) {
   int64_t node_score = 0, wsum = 0;
   for (int i = 0; i < st.n_rtcr; ++i) {
@@ -411,9 +426,7 @@ __device__ __forceinline__ int64_t rtcr_score(const DevState& st, const kgpu_pod
     }
   }
   if (wsum == 0) return 0;
-  // math.Round(float64(a) / float64(b)) for 0 <= a, 0 < b: a / b is never within an ulp of a .5
-  // that it does not equal, so the exact half-away-from-zero integer rounding is the same value
-  return (2 * node_score + wsum) / (2 * wsum);
+  return rtcr_round(node_score, wsum);
 }
 
 // NodeResourceLimits (resource_limits.go:104-160): 1 when the pod's cpu or memory limit fits the
@@ -433,6 +446,58 @@ __device__ __forceinline__ int64_t balanced_score(const kgpu_pod_query& q, const
   if (cf >= 1.0 || mf >= 1.0) return 0;
   const double diff = fabs(cf - mf);
   return (int64_t)((1.0 - diff) * 100.0);
+}
+
+// kgpu_debug_arith: one of the score arithmetic's inline functions above per element, the functions the
+// kernels call.  The reciprocals come from set_recips, as the persistent rows' do; the exact forms are
+// what load_res's zero reciprocals select.  out = the value, flag = ratio100's / least_def's / most_def's
+// `slow` (0 for the other ops).
+__global__ void k_dbg_arith(int op, const int64_t* __restrict__ a, const int64_t* __restrict__ b,
+                            const int64_t* __restrict__ c, const int64_t* __restrict__ d, int64_t* __restrict__ out,
+                            int32_t* __restrict__ flag, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t A = a[i], Bv = b[i], Cv = c[i], Dv = d[i];
+  NodeRes nr{};
+  int64_t v = 0;
+  bool slow = false;
+  switch (op) {
+    case KGPU_ARITH_DIV_NONNEG: v = div_nonneg(A, Bv); break;
+    case KGPU_ARITH_WDIV: v = wdiv(A, Bv); break;
+    case KGPU_ARITH_HALF: v = half(A); break;
+    case KGPU_ARITH_LEAST_ONE: v = least_one(A, Bv); break;
+    case KGPU_ARITH_MOST_ONE: v = most_one(A, Bv); break;
+    case KGPU_ARITH_LEAST_RECIP:
+    case KGPU_ARITH_MOST_RECIP:
+      nr.ac = A;
+      nr.am = Cv;
+      set_recips(nr);
+      v = op == KGPU_ARITH_LEAST_RECIP ? least_def(nr, Bv, Dv, slow) : most_def(nr, Bv, Dv, slow);
+      break;
+    case KGPU_ARITH_RATIO100:
+      nr.ac = Bv;
+      set_recips(nr);
+      v = ratio100(A, Bv, nr.ic, slow);
+      break;
+    case KGPU_ARITH_RATIO100_32:
+      nr.ac = Bv;
+      set_recips(nr);
+      v = ratio100_32((int32_t)A, (int32_t)Bv, nr.ic);
+      break;
+    case KGPU_ARITH_BALANCED: {
+      kgpu_pod_query q{};
+      nr.ac = A;
+      nr.zc = Bv;
+      nr.am = Cv;
+      nr.zm = Dv;
+      v = balanced_score(q, nr);
+      break;
+    }
+    case KGPU_ARITH_RTCR_ROUND: v = rtcr_round(A, Bv); break;
+    default: break;
+  }
+  out[i] = v;
+  flag[i] = slow ? 1 : 0;
 }
 
 __device__ __forceinline__ int64_t image_score(const DevState& st, const kgpu_pod_query& q, int n) {
@@ -2614,6 +2679,13 @@ int launch_debug_broken_linear(const kgpu_shape_point* pts, int n_pts, const int
   for (int i = 0; i < n_pts; ++i) s.pts[i] = pts[i];
   s.n = n_pts;
   hipLaunchKernelGGL(k_dbg_broken_linear, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, s, p, out, n);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_debug_arith(int op, const int64_t* a, const int64_t* b, const int64_t* c, const int64_t* d, int64_t* out,
+                       int32_t* flag, int n, void* stream) {
+  if (op < 0 || op >= KGPU_ARITH_OPS || n <= 0) return -1;
+  hipLaunchKernelGGL(k_dbg_arith, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, a, b, c, d, out, flag, n);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -25,7 +25,7 @@ EXPORTS = ["kgpu_abi_version", "kgpu_struct_sizes", "kgpu_create", "kgpu_destroy
            "kgpu_debug_wg_trace", "kgpu_debug_topo_resident",
            "kgpu_next_slot", "kgpu_adopt_pod", "kgpu_prepare_pods", "kgpu_filter_reasons", "kgpu_debug_counters",
            "kgpu_schedule_batch_submit", "kgpu_schedule_batch_wait", "kgpu_pipelined",
-           "kgpu_geometry_for", "kgpu_debug_geometry", "kgpu_debug_instantiation"]
+           "kgpu_geometry_for", "kgpu_debug_geometry", "kgpu_debug_instantiation", "kgpu_debug_arith"]
 
 
 class KgpuError(RuntimeError):
@@ -86,6 +86,7 @@ def lib():
     L.kgpu_geometry_for.argtypes = [i32, i32, i32, i32, vp]
     L.kgpu_debug_geometry.argtypes = [vp, vp]
     L.kgpu_debug_instantiation.argtypes = [vp, vp]
+    L.kgpu_debug_arith.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32]
     L.kgpu_filter_reasons.argtypes = [vp, C.POINTER(abi.ReasonArgs), vp, i64, C.POINTER(i64)]
     if L.kgpu_abi_version() != abi.ABI_VERSION:
         raise KgpuError(abi.E_STATE, "ABI version mismatch")
@@ -105,6 +106,10 @@ def check_layout(L=None):
         raise KgpuError(abi.E_STATE, "struct layout mismatch (python, C): %r" % bad)
     return True
 
+
+# kgpu_debug_arith ops (include/kgpu.h KGPU_ARITH_*)
+ARITH_OPS = ("div_nonneg", "wdiv", "half", "least_one", "most_one", "least_recip", "most_recip", "ratio100",
+             "ratio100_32", "balanced", "rtcr_round")
 
 KERNEL_BATCH, KERNEL_TBATCH = 1, 2  # kgpu_geometry_for / kgpu_debug_geometry kernel ids
 _GEO_KERNELS = {0: None, KERNEL_BATCH: "k_batch", KERNEL_TBATCH: "k_tbatch"}
@@ -382,6 +387,21 @@ class Engine:
         out = np.zeros(len(p), np.int64)
         self._check(lib().kgpu_debug_broken_linear(self.h, pts, len(points), p.ctypes.data, len(p), out.ctypes.data))
         return [int(x) for x in out]
+
+    def arith(self, op, a, b=None, c=None, d=None):
+        """kgpu_debug_arith: the device's own score arithmetic function `op` (a name of ARITH_OPS) over
+        int64 operand arrays, one launch; operands an op does not name default to 0.  Returns (values
+        int64, flags int32): the flag is the reciprocal forms' `slow` (least_recip, most_recip,
+        ratio100), 0 elsewhere.  Preconditions: include/kgpu.h."""
+        a = np.ascontiguousarray(a, np.int64)
+        ops = [a] + [np.zeros(len(a), np.int64) if x is None else np.ascontiguousarray(x, np.int64) for x in (b, c, d)]
+        if any(x.shape != a.shape or x.ndim != 1 for x in ops):
+            raise ValueError("operand arrays of one length")
+        out = np.zeros(len(a), np.int64)
+        flag = np.zeros(len(a), np.int32)
+        self._check(lib().kgpu_debug_arith(self.h, ARITH_OPS.index(op), *[x.ctypes.data for x in ops],
+                                           out.ctypes.data, flag.ctypes.data, len(a)))
+        return out, flag
 
     def xgmi_active(self):
         return bool(lib().kgpu_xgmi_active(self.h))

@@ -80,8 +80,8 @@ GENERIC_SHAPE = {0: (300, 0), 1: (300, 0), 2: (300, 0), 3: (300, 0), 4: (300, 0)
 TOPO_SHAPE = {0: (1500, 1), 1: (1500, 1), 2: (1500, 1), 3: (2048, 0), 4: (4096, 4)}
 
 
-def _generic(seed, n_nodes):
-    nodes, existing, pods = gen_random.cluster(seed, n_nodes=n_nodes, n_existing=400, n_pods=120)
+def _generic(seed, n_nodes, n_existing=400):
+    nodes, existing, pods = gen_random.cluster(seed, n_nodes=n_nodes, n_existing=n_existing, n_pods=120)
     for n in nodes:
         taints = [t for t in n["spec"].get("taints", []) if t["effect"] != "PreferNoSchedule"]
         if taints:
@@ -119,11 +119,14 @@ class _Ref:
     """One cluster under one profile: compiled once, scheduled once by the C restatement; the cases
     that share it (the geometries of one cluster size) leave it unchanged."""
 
-    def __init__(self, family, seed, n_nodes, prof):
+    def __init__(self, family, seed, n_nodes, prof, inputs=None, profile=None):
+        """inputs, profile: another generator's (nodes, existing, pods, cluster) of the same family and a
+        profile object outside PROFILES (tests/test_numeric_range.py)."""
         from oracle.cref import RefEngine
-        nodes, existing, pods, cl = (_generic if family == "generic" else _topo)(seed, n_nodes)
+        nodes, existing, pods, cl = inputs or (_generic if family == "generic" else _topo)(seed, n_nodes)
         self.family, self.n_nodes = family, n_nodes
-        self.fw = GpuFramework(PROFILES[prof][0](), nodes, existing, cluster=cl, pods_hint=pods, create_engine=False)
+        self.fw = GpuFramework(profile or PROFILES[prof][0](), nodes, existing, cluster=cl, pods_hint=pods,
+                               create_engine=False)
         self.q, self.pc, _, errs = self.fw.compile_pods(pods)
         assert not errs
         ref = RefEngine(self.fw.config, self.fw.snap, threads=4)
