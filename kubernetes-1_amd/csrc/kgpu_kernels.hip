@@ -35,6 +35,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 #include "kgpu_internal.h"
 
@@ -1590,12 +1591,58 @@ struct HRow {
   double ic, im;
 };
 
+// The query ring of the helper-wave instantiation: pod k's record sits in LDS slot k & (kQRing - 1), and
+// inside the pod loops no wave loads a query from memory.  The prologue stages pods 0..2; in iteration i
+// the communication wave loads pod i + 3 (the load that used to warm L2) and writes it to its slot once it
+// has published pod i, off its resolve -> publish chain.  The row wave and the helper waves read pod i + 1
+// at the top of iteration i: LDS returns in order, so those reads are complete when the wait before
+// barrier (c) has covered the iteration's own LDS writes.  Pod k is therefore written after barrier (c) of
+// iteration k - 3 (which its writer passes before barrier (c) of iteration k - 2), read after barrier (c)
+// of iteration k - 2 and before that of iteration k - 1 (the communication wave reads its two counts once
+// more, at the top of iteration k + 1), and its slot is rewritten, with pod k + 4, after barrier (c) of
+// iteration k + 1 by that same wave.
+constexpr int kQRing = 4;
+constexpr int kQWords = (int)(sizeof(kgpu_pod_query) / 8);
+static_assert(kQWords <= 64, "one query row per vector load");
+typedef uint64_t __attribute__((may_alias)) qword_t;  // a query record as kQWords 8-byte words
+struct NoQuery {};  // what stands for a ring record in the instantiations without a ring
+// What the three wave roles read of pod k's record, as vector registers.  EVERY OTHER FIELD OF THE RESULT
+// IS ZERO.  The list is what the helper-wave instantiation's profile reads -- k_batch's static_assert pins
+// it to NodeResourcesFit + LeastAllocated + BalancedAllocation over {cpu, memory}: fit_detail (flags, req,
+// scalars), least_def / balanced_score (score_req[0..1]), assume_row / assume_regs (req, nz, scalars,
+// ports), the slow-path test (scalars.count | ports.count).  A profile or a reader that takes another
+// field needs it added here first.
+__device__ __forceinline__ kgpu_pod_query ring_read(const kgpu_pod_query* ring, int k) {
+  const kgpu_pod_query& s = ring[k & (kQRing - 1)];
+  kgpu_pod_query q{};
+  q.flags = s.flags;
+  q.req[0] = s.req[0]; q.req[1] = s.req[1]; q.req[2] = s.req[2];
+  q.nz[0] = s.nz[0]; q.nz[1] = s.nz[1];
+  q.score_req[0] = s.score_req[0]; q.score_req[1] = s.score_req[1];
+  q.scalars = s.scalars;
+  q.ports = s.ports;
+  return q;
+}
+// The fields that steer branches and the scalar loads of the pools made wave-uniform again (every
+// lane read the same LDS words).  The 64-bit quantities stay in vector registers.
+__device__ __forceinline__ kgpu_pod_query ring_uniform(kgpu_pod_query q) {
+  q.flags = __builtin_amdgcn_readfirstlane(q.flags);
+  q.scalars.begin = __builtin_amdgcn_readfirstlane(q.scalars.begin);
+  q.scalars.count = __builtin_amdgcn_readfirstlane(q.scalars.count);
+  q.ports.begin = __builtin_amdgcn_readfirstlane(q.ports.begin);
+  q.ports.count = __builtin_amdgcn_readfirstlane(q.ports.count);
+  return q;
+}
+
 // XG: the node-sharded instantiation (xGMI mailbox rings); the unsharded one carries none of its code.
-template <uint32_t FM, uint32_t SM, int K, int B, bool XG, bool HB = false>
+// TR (helper-wave instantiation only): the phase stamps are compiled in; without it that instantiation
+// carries none.  The others test BatchArgs.trace at run time.
+template <uint32_t FM, uint32_t SM, int K, int B, bool XG, bool HB = false, bool TR = false>
 __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevState* __restrict__ stp, BatchArgs pa) {
   static_assert(!HB || (B == 64 && !XG &&
                        SM == ((1u << KGPU_S_BALANCED_ALLOCATION) | (1u << KGPU_S_LEAST_ALLOCATED) | kDefRes)),
                 "the helper wave splits config (b)'s profile on the one-row-wave geometry");
+  static_assert(HB || !TR, "only the helper-wave instantiation has a traced twin");
   const DevState& st = *stp;
   constexpr int W = B / 64;  // row waves; wave W communicates; HB: waves W + 1, W + 2 help row wave 0
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1608,6 +1655,7 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
   __shared__ BatchShared<B> sh;
   __shared__ int64_t sh_hk[HB ? 2 * 2 * K * B : 1];  // HB: [helper][pod parity][slot][lane] weighted score
   __shared__ int sh_hready[2];                       // HB: i + 1 once pod i's parts of helper h are in sh_hk
+  __shared__ std::conditional_t<HB, kgpu_pod_query, NoQuery> sh_q[HB ? kQRing : 1];  // HB: the query ring
   __shared__ uint64_t* sh_peer_g[XG ? kMaxRanks : 1];
   __shared__ int32_t* sh_peer_f[XG ? kMaxRanks : 1];
   if constexpr (XG) {
@@ -1621,6 +1669,11 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
     sh.cready = 0;
     sh_hready[0] = 0;
     sh_hready[1] = 0;
+  }
+  if constexpr (HB) {
+    if (wave == W && lane < kQWords)
+      for (int k = 0; k < 3 && k < pa.count; ++k)
+        reinterpret_cast<qword_t*>(&sh_q[k])[lane] = ((const GAS qword_t*)(st.queries + pa.first + k))[lane];
   }
   __syncthreads();
   auto ring_row = [&](int k) -> size_t { return xg ? (size_t)((pa.xseq0 + k) % pa.R) : (size_t)k; };
@@ -1647,8 +1700,9 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
   // communication wave: 7 pod i-1 resolved, 6 pod i's partials complete, 3 pod i published.
   const bool tr = pa.trace && (g == 0 || g == G - 1);
   int64_t* trow = pa.trace ? pa.trace + (g == 0 ? 0 : 8) : nullptr;
+  constexpr bool kStamps = !HB || TR;
 #define KGPU_STAMP(i, k) \
-  if (tr && (tid == 0 || tid == B)) trow[(size_t)(i) * 16 + (k)] = (int64_t)__builtin_amdgcn_s_memrealtime()
+  if (kStamps && tr && (tid == 0 || tid == B)) trow[(size_t)(i) * 16 + (k)] = (int64_t)__builtin_amdgcn_s_memrealtime()
 
   if constexpr (HB) {
     if (wave == W + 1 || wave == W + 2) {
@@ -1674,12 +1728,12 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       const int64_t wl = st.w_of[KGPU_S_LEAST_ALLOCATED], wbal = st.w_of[KGPU_S_BALANCED_ALLOCATION];
       int cand = -1;
       bool staged = false;
+      kgpu_pod_query rq = ring_uniform(ring_read(sh_q, 0)), rqp{};  // pod i, pod i-1 (have_cur, have_prev)
       for (int i = 0; i <= pa.count; ++i) {
         const bool have_prev = i > 0, have_cur = i < pa.count;
         const int p = i & 1;
-        const kgpu_pod_query* qc = st.queries + pa.first + i;       // pod i (have_cur)
-        const kgpu_pod_query* qpp = st.queries + pa.first + i - 1;  // pod i-1 (have_prev)
-        const bool qmem = have_prev && (cp(qpp)->scalars.count | cp(qpp)->ports.count) != 0;
+        const kgpu_pod_query rqn = ring_read(sh_q, i + 1);  // consumed after barrier (c)
+        const bool qmem = have_prev && (rqp.scalars.count | rqp.ports.count) != 0;
         const bool fast_b = have_prev && cand >= 0 && staged && pa.assume && !qmem;
         const int ob = cand >= 0 ? cand % B : -1, jb = cand >= 0 ? cand / B : -1;
         if (have_cur) {
@@ -1691,16 +1745,16 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
               if (j == jb) {
                 t.ac = lane64(h[j].ac, ob);
                 t.am = lane64(h[j].am, ob);
-                t.zc = lane64(h[j].zc, ob) + cp(qpp)->nz[0];
-                t.zm = lane64(h[j].zm, ob) + cp(qpp)->nz[1];
+                t.zc = lane64(h[j].zc, ob) + rqp.nz[0];
+                t.zm = lane64(h[j].zm, ob) + rqp.nz[1];
                 t.ic = __builtin_bit_cast(double, lane64(__builtin_bit_cast(int64_t, h[j].ic), ob));
                 t.im = __builtin_bit_cast(double, lane64(__builtin_bit_cast(int64_t, h[j].im), ob));
               }
             if (lane == B - 1) h[K - 1] = t;
           }
           kgpu_pod_query qh;
-          qh.score_req[0] = cp(qc)->score_req[0];
-          qh.score_req[1] = cp(qc)->score_req[1];
+          qh.score_req[0] = rq.score_req[0];
+          qh.score_req[1] = rq.score_req[1];
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             const bool spare = spare_slot(j, K, lane, B);
@@ -1723,10 +1777,12 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
 #pragma unroll
           for (int j = 0; j < K; ++j)
             if (j == jb) {
-              h[j].zc += cp(qpp)->nz[0];
-              h[j].zm += cp(qpp)->nz[1];
+              h[j].zc += rqp.nz[0];
+              h[j].zm += rqp.nz[1];
             }
         }
+        rqp = rq;
+        rq = ring_uniform(rqn);
         const bool slow = have_cur && won && pa.assume && !fast_b;
         int cn = -1;
         if (have_cur && !slow) {
@@ -1748,23 +1804,30 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
     // ---- communication wave: resolve pod i-1 while the row waves evaluate pod i, then combine
     //      their partials and publish pod i (variant B when this workgroup won pod i-1), and write
     //      pod i-1's result record
-    constexpr int kQWords = (int)(sizeof(kgpu_pod_query) / 8);
-    static_assert(kQWords <= 64, "one query row per prefetch instruction");
     int cand = -1;        // this workgroup's candidate for pod i-1 (what it published)
     bool staged = false;  // its row is staged for variant B
     for (int i = 0; i <= pa.count; ++i) {
       const bool have_prev = i > 0, have_cur = i < pa.count;
       const int p = i & 1;
       if (i == pa.abort_at && g == 0 && lane == 0) __hip_atomic_store(pa.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // pod i+2's query into L2 (the row waves' scalar load of it, an iteration later, then hits)
-      if (i + 2 < pa.count) {
+      // pod i+2's query into L2 (the row waves' scalar load of it, an iteration later, then hits).  HB: no
+      // wave loads a query in its loop -- this is the load of pod i+3's record for the query ring (kQRing)
+      uint64_t qv = 0;
+      if constexpr (HB) {
+        if (i + 3 < pa.count && lane < kQWords) qv = ((const GAS qword_t*)(st.queries + pa.first + i + 3))[lane];
+      } else if (i + 2 < pa.count) {
         const uint64_t v = lane < kQWords ? reinterpret_cast<const uint64_t*>(st.queries + pa.first + i + 2)[lane] : 0;
         asm volatile("" ::"v"(v));
       }
       bool qmem = false;  // pod i-1 carries extended resources or host ports: no variant B
       if (have_prev) {
-        const kgpu_pod_query* qq = st.queries + pa.first + i - 1;
-        qmem = (cp(qq)->scalars.count | cp(qq)->ports.count) != 0;
+        if constexpr (HB) {
+          const kgpu_pod_query& qq = sh_q[(i - 1) & (kQRing - 1)];
+          qmem = __builtin_amdgcn_readfirstlane(qq.scalars.count | qq.ports.count) != 0;
+        } else {
+          const kgpu_pod_query* qq = st.queries + pa.first + i - 1;
+          qmem = (cp(qq)->scalars.count | cp(qq)->ports.count) != 0;
+        }
       }
       const bool fast_b = have_prev && cand >= 0 && staged && pa.assume && !qmem;
       uint64_t wkey = 0;
@@ -1819,6 +1882,10 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
         KGPU_STAMP(i, 3);
         cn = c.key ? c.idx : -1;
       }
+      if constexpr (HB) {
+        // past barrier (c) of iteration i and off the resolve -> publish chain (kQRing)
+        if (i + 3 < pa.count && lane < kQWords) reinterpret_cast<qword_t*>(&sh_q[(i + 3) & (kQRing - 1)])[lane] = qv;
+      }
       if (slow) {
         lds_wait(&sh.cready, i + 1, pa.abort);
         cand = sh.cslow[p];
@@ -1856,10 +1923,17 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
 
   kgpu_pod_query qp{};                      // pod i-1 (published, not yet resolved)
   kgpu_pod_query q = *cp(st.queries + pa.first);
+  // (HB: out of the ring; the load above is then dead.  Written so that the instantiations without a ring
+  // compile to what they were: an initialisation through a second statement or a lambda moved their
+  // register allocation)
+  if constexpr (HB) q = ring_uniform(ring_read(sh_q, 0));
   int cand = -1;                            // this workgroup's candidate for pod i-1 (uniform)
   bool staged = false;                      // its row is (being) staged in sh.brow[(i-1) & 1]
   for (int i = 0; i <= pa.count; ++i) {
     KGPU_STAMP(i, 0);
+    // HB: pod i+1's record out of the query ring (kQRing), consumed after barrier (c); nothing otherwise
+    std::conditional_t<HB, kgpu_pod_query, NoQuery> qraw{};
+    if constexpr (HB) qraw = ring_read(sh_q, i + 1);
     const bool have_prev = i > 0;
     const bool have_cur = i < pa.count;
     const int p = i & 1;
@@ -1923,12 +1997,15 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       wg_partials<K, B>(sh, p, keys, fast_b, ob, jb, cand, own_a, own_b);
     }
     KGPU_STAMP(i, 1);
-    // the next pod's query: issued now, consumed after the barrier.  (Issued before the evaluation
+    // the next pod's query (HB: it came out of the query ring at the top of the iteration, kQRing):
+    // issued now, consumed after the barrier.  (Issued before the evaluation
     // instead, it costs config (a)'s default-profile kernel 2.77 -> 2.93 us per pod -- the query's
     // fields then stay live through the evaluation -- and gains config (b) nothing once the
     // variant-B row is read across lanes: profiles/r03_qn_bench.jsonl.)
     kgpu_pod_query qn{};
-    if (i + 1 < pa.count) qn = *cp(st.queries + pa.first + i + 1);
+    if constexpr (!HB) {
+      if (i + 1 < pa.count) qn = *cp(st.queries + pa.first + i + 1);
+    }
     __syncthreads();  // (c): pod i-1 resolved and pod i published (communication wave)
     KGPU_STAMP(i, 2);
     int wg = -1;
@@ -1936,6 +2013,9 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       const int s = (i - 1) & 1;
       if (sh.rabort[s]) break;
       wg = sh.rwg[s];
+    }
+    if constexpr (HB) {
+      if (i + 1 < pa.count) qn = ring_uniform(qraw);
     }
     const bool won = have_prev && wg == gme;
     // pod i's candidate: what the communication wave publishes (the same combine of the partials),
@@ -4391,15 +4471,23 @@ using BatchFn = void (*)(const DevState*, BatchArgs);
 // the helper-wave instantiation (HB) of config (b)'s profile on the one-row-wave geometry
 template <uint32_t FM, uint32_t SM, bool E>
 struct HelperFn {
-  static constexpr BatchFn fn = nullptr;
+  static constexpr BatchFn fn = nullptr, traced = nullptr;
 };
 template <uint32_t FM, uint32_t SM>
 struct HelperFn<FM, SM, true> {
   static constexpr BatchFn fn = k_batch<FM, SM, 1, 64, false, true>;
+  // its twin with the phase stamps compiled in (BatchArgs.trace set: KGPU_OPT_PHASE_TRACE)
+  static constexpr BatchFn traced = k_batch<FM, SM, 1, 64, false, true, true>;
 };
 static const BatchFn kBatchHelper[] = {
     nullptr,
     HelperFn<kFitFM, kFitSM, true>::fn,
+    nullptr,
+    nullptr,
+};
+static const BatchFn kBatchHelperTraced[] = {
+    nullptr,
+    HelperFn<kFitFM, kFitSM, true>::traced,
     nullptr,
     nullptr,
 };
@@ -4458,10 +4546,11 @@ int launch_batch(const DevState* st, const BatchArgs& a, int groups, int geo, in
   // from stacking two persistent workgroups on one CU (they would share its SIMDs).
   const int x = a.R > 0 ? 1 : 0;  // node-sharded over xGMI mailboxes
   const bool hb = batch_helper_used(spec, geo, x != 0, helper);
-  const BatchFn fn = hb ? kBatchHelper[spec] : (x ? kBatchX : kBatch)[spec][geo];
+  const bool traced = hb && a.trace != nullptr;
+  const BatchFn fn = hb ? (traced ? kBatchHelperTraced : kBatchHelper)[spec] : (x ? kBatchX : kBatch)[spec][geo];
   const int threads = kGeo[geo].B + 64 + (hb ? 2 * kGeo[geo].B : 0);
-  static bool attr_set[3][kNumSpecs][kNumGeo] = {};
-  const int ai = hb ? 2 : x;
+  static bool attr_set[4][kNumSpecs][kNumGeo] = {};
+  const int ai = hb ? (traced ? 3 : 2) : x;
   if (!attr_set[ai][spec][geo]) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kBatchLdsPad) != hipSuccess)
