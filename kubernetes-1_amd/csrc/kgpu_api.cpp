@@ -268,6 +268,9 @@ struct kgpu_ctx {
   bool force_coop = false;          // a call issued again after a clean abort (every persistent launch
                                     // of it cooperative)
   int32_t hold_group = -1;          // KGPU_OPT_HOLD_GROUP test hook
+  bool cut_persistent = true;       // KGPU_OPT_CUT_PERSISTENT
+  DevBuf cgran;                     // cut-mode persistent runs: count and key granules, position words
+  int64_t n_cut_pods = 0;           // kgpu_debug_counters: pods resolved inside cut-mode persistent launches
   bool tbatch_wlab = true;          // KGPU_OPT_TBATCH_WLAB
   bool tbatch_sleep = true;         // KGPU_OPT_TBATCH_POLL_SLEEP
   bool run_all = false;             // KGPU_OPT_RUN_ALL_FILTERS
@@ -2233,7 +2236,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     return fail(c, KGPU_E_UNSUPPORTED, "percentageOfNodesToScore < 100 on a node-sharded engine (nextStartNodeIndex "
                                        "rotates over the whole cluster): use 100 when sharding");
   int kidx = -1;
-  if (c->persistent && !diag && !cut && !nom_dev) {
+  if (c->persistent && !diag && (!cut || c->cut_persistent) && !nom_dev) {
     if (xg) {
       kidx = c->xg_geo;
       per = c->xg_per;
@@ -2269,6 +2272,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     return KGPU_OK;
   };
   bool used_persistent = false;
+  int64_t cut_pods = 0;  // this call's pods inside cut-mode runs (taken back when the call is issued again)
   int32_t* done_word = nullptr;  // the pinned completion word of the call's last kernel (one-pod cycles)
   // one abort word for every persistent run of this batch (OR-ed on the device)
   int rc_abort = ensure(c, c->abort_buf, 64);
@@ -2410,10 +2414,24 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     }
     if (kidx >= 0 && !norm[(size_t)i]) {
       // a run of pods with constant normalize maxima: one persistent launch
-      while (j < n && !norm[(size_t)j] && !topo[(size_t)j] && (!xg || j - i < kgpu::kXgmiRing / 2)) ++j;
+      // (a cut run's granule area is capped at 64 MiB: a longer run continues in another launch, which
+      // takes up the rotation from cut_state)
+      const int32_t max_run = cut ? (int32_t)std::max<size_t>(1, ((size_t)64 << 20) / (16 * (size_t)groups + 8)) : INT32_MAX;
+      while (j < n && !norm[(size_t)j] && !topo[(size_t)j] && (!xg || j - i < kgpu::kXgmiRing / 2) && j - i < max_run) ++j;
       const int32_t cnt = j - i;
       kgpu::BatchArgs ba{};
-      if (xg) {
+      if (cut) {
+        // layout: granules [cnt][2][groups] u64 | position words [cnt] u64, all zeroed
+        const size_t cells = (size_t)cnt * 2 * (size_t)groups;
+        const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
+        if ((rc = ensure(c, c->cgran, gbytes))) return rc;
+        HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
+        ba.cgran = static_cast<uint64_t*>(c->cgran.p);
+        ba.cpos = ba.cgran + cells;
+        ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
+        ba.nranks = 1;
+        ba.GT = groups;
+      } else if (xg) {
         // every rank's mailbox ring (kgpu_xgmi_init); rows are addressed by the ring sequence
         const size_t cells = (size_t)kgpu::kXgmiRing * (size_t)c->xg_GT;
         ba.gran = static_cast<uint64_t*>(c->xg_box.p);
@@ -2467,8 +2485,13 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       ++c->state_launches;
       note_geometry(c, 1, kidx, groups, per);
       note_instantiation(c, kgpu::batch_row(c->spec), ba.R > 0,
-                         kgpu::batch_helper_used(c->spec, kidx, ba.R > 0, c->batch_helper), cnt);
-      if (kgpu::launch_batch(dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
+                         !cut && kgpu::batch_helper_used(c->spec, kidx, ba.R > 0, c->batch_helper), cnt);
+      if (cut) {
+        c->n_cut_pods += cnt;
+        cut_pods += cnt;
+        if (kgpu::launch_cbatch(dst, ba, groups, kidx, c->spec, coop, c->stream))
+          return fail(c, KGPU_E_DEVICE, "k_cbatch launch failed");
+      } else if (kgpu::launch_batch(dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
         return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
       if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
       ev += 2;
@@ -2618,6 +2641,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     // buffer may be half zeroed: both buffers are recomputed from zeros by the next run.
     c->tc.valid = false;
     for (int k = 0; k < 2; ++k) c->tc.dirty[k] = c->tc.buf[k].bytes;
+    c->n_cut_pods -= cut_pods;
     return kCleanAbort;
   }
   c->port_bound += batch_ports;
@@ -3750,7 +3774,7 @@ int kgpu_destroy(kgpu_ctx* c) try {
   free_all(c->work_allocs);
   for (DevBuf* b : {&c->dstate, &c->ticket, &c->queries, &c->pool_blk, &c->results, &c->gran, &c->trace, &c->d_classes,
                     &c->d_citems, &c->d_tclasses, &c->d_creqs, &c->d_cints, &c->d_plans, &c->d_aux,
-                    &c->d_aux_terms, &c->scratch, &c->d_pods, &c->gbar, &c->cut_buf, &c->t_tables, &c->t_zero,
+                    &c->d_aux_terms, &c->scratch, &c->d_pods, &c->gbar, &c->cut_buf, &c->cgran, &c->t_tables, &c->t_zero,
                     &c->abort_buf, &c->flags_buf, &c->d_stage, &c->d_remap, &c->d_from,
                     &c->p_args, &c->p_voff, &c->p_veff, &c->p_noff, &c->p_neff, &c->p_aux, &c->p_vrecs,
                     &c->p_vsc, &c->p_vports, &c->p_nrecs, &c->p_nsc, &c->p_nports, &c->p_vstate, &c->p_order,
@@ -3812,9 +3836,10 @@ int kgpu_read_phase_trace(kgpu_ctx* c, int64_t* out, int32_t max_pods) try {
 
 int kgpu_debug_counters(const kgpu_ctx* c, int64_t* out, int32_t n) {
   if (!c || (n > 0 && !out)) return KGPU_E_INVAL;
-  const int64_t v[5] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full};
-  for (int32_t i = 0; i < n && i < 5; ++i) out[i] = v[i];
-  return 5;
+  const int64_t v[6] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
+                        c->n_cut_pods};
+  for (int32_t i = 0; i < n && i < 6; ++i) out[i] = v[i];
+  return 6;
 }
 
 int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]) try {
@@ -3901,6 +3926,7 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_ZEROCOPY_POOLS) c->zc_pools = value != 0;
   else if (option == KGPU_OPT_RUN_ALL_FILTERS) c->run_all = value != 0;
   else if (option == KGPU_OPT_HOLD_GROUP) c->hold_group = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
+  else if (option == KGPU_OPT_CUT_PERSISTENT) c->cut_persistent = value != 0;
   else if (option == KGPU_OPT_SKIP_RELEASE_AT) c->skip_release_at = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else return KGPU_E_INVAL;
   return KGPU_OK;

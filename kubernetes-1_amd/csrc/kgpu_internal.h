@@ -294,6 +294,15 @@ struct BatchArgs {
   int32_t GT;              // granules per pod row: nranks * groups
   int32_t R;               // ring rows, 0 = linear rows
   int64_t xseq0;
+  // Cut mode (k_cbatch, percentageOfNodesToScore < 100; null / 0 otherwise).  to_find and cut_state come
+  // with DevState.  cgran: [count][2][groups] granules, round 1 (feasible counts) and round 2 (keys) of
+  // every pod; cpos: [count] position words (valid | p, written by the workgroup that holds rank
+  // to_find + 1); both zeroed before the launch.  The kernel writes every field of a pod's record itself
+  // (feasible = min(total, to_find), evaluated = p): no side array, no k_batch_fixup.
+  uint64_t* cgran;
+  uint64_t* cpos;
+  int32_t cut_nofilt;      // the profile has no filter plugins: ranks in non-rotated order
+  int32_t pad_c;
 };
 // abort word codes (OR-ed): a spin gave up before the run resolved its first pod (nothing on the device
 // changed) / after it
@@ -550,6 +559,10 @@ int launch_batch(const DevState* st, const BatchArgs& a, int groups, int kidx, i
 // What launch_batch indexes (kgpu_debug_instantiation): the profile row for `spec`, and whether the
 // launch takes the helper-wave instantiation (sharded: BatchArgs.R > 0).
 int batch_row(int spec);
+// The cut-mode sibling (k_cbatch: BatchArgs.cgran / cpos set, to_find < N) on the same geometry table and
+// profile rows, every geometry; B threads per workgroup (no communication wave, no helper waves), no
+// k_batch_fixup.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured as in k_batch.
+int launch_cbatch(const DevState* st, const BatchArgs& a, int groups, int kidx, int spec, bool coop, void* stream);
 bool batch_helper_used(int spec, int geo, bool sharded, bool helper);
 // Topology pipeline for one pod (PodArgs.pod): domain histograms, critical-path minima, filters,
 // scores, normalize + argmax, resolve + assume.  next_scratch: words of the next topology pod's

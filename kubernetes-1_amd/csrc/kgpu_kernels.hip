@@ -2124,6 +2124,267 @@ __global__ __launch_bounds__(256) void k_batch_fixup(const DevState* __restrict_
   }
 }
 
+// ---------------------------------------------------------------- persistent batch kernel, cut mode
+// k_batch's sibling for percentageOfNodesToScore < 100 (the rule above k_cut): a run of pods in ONE
+// launch, workgroup g owning nodes [g*per, (g+1)*per) as in k_batch (same geometry table; the spare
+// slot stays empty).  Whether a node is kept depends on the feasible counts of every workgroup before
+// it in rotated order, so a pod takes two exchanges of write-through granules:
+//   round 1  counts: valid | hi << 20 | lo -- this workgroup's feasible nodes with index >= s (hi) and
+//            < s (lo), s = nextStartNodeIndex.  Every workgroup sums the complete row: its first hi rank
+//            is the hi of the groups before it, its first lo rank all hi plus the lo before it.  Inside
+//            the workgroup ranks come from ballots and the per-(slot, wave) prefixes in LDS.  Rank
+//            <= to_find is kept; the lane holding rank to_find + 1 knows p, its rotated position.
+//   round 2  keys: valid | ((score+1) << 40 | rank40) of the best KEPT node (scores run only in waves
+//            that hold a kept node); the owner of rank to_find + 1 also publishes valid | p in the
+//            pod's position word (when total <= to_find, p = N and nobody publishes).  Everyone
+//            resolves the winner and reads p; the winning workgroup assumes and writes the record;
+//            all advance s by p.
+// A profile without filters ranks in non-rotated order (s taken as 0 for the ranks): every node is
+// feasible, so rank to_find + 1 sits at position to_find and p = to_find falls out of the same rule.
+// No speculation: pod i's filters start after pod i-1 is assumed.  A poll that outlives kSpinTimeout
+// raises the abort word: kAbortClean in round 1 of the run's first pod (nothing changed), dirty from
+// that pod's round 2 on (a workgroup may have assumed).  cut_state is read at run start and written by
+// workgroup 0 at run end, so per-pod launches and further runs continue the rotation.
+template <int NJ>
+__device__ __forceinline__ bool poll_counts(const uint64_t* row, int G, int g, const int32_t* abort_word,
+                                            uint32_t (&out)[4]) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+  for (;;) {
+    const Sweep<NJ> a = sweep<NJ, false>(row, G, abort_word, kGValid);
+    if (__any(a.abort != 0)) return false;
+    bool all = true;
+    uint32_t hb = 0, lb = 0, ha = 0, la = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const uint64_t v = a.v[j];
+      if (!(v & kGValid)) all = false;
+      const uint32_t hi = (uint32_t)(v >> 20) & 0xFFFFFu, lo = (uint32_t)v & 0xFFFFFu;
+      ha += hi;
+      la += lo;
+      if (lane + 64 * j < g) {
+        hb += hi;
+        lb += lo;
+      }
+    }
+    if (__all(all)) {
+      out[0] = wave_sum32(hb);
+      out[1] = wave_sum32(lb);
+      out[2] = wave_sum32(ha);
+      out[3] = wave_sum32(la);
+      return true;
+    }
+    if (__builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) return false;
+  }
+}
+
+template <int K, int B>
+struct CutShared {
+  static constexpr int W = B / 64;
+  int chi[K * W], clo[K * W];  // feasible counts per (slot, wave), then their exclusive prefixes
+  int base_hi, base_lo, tot_hi, tot_lo;
+  int pown;                    // p when this workgroup holds rank to_find + 1, else -1
+  uint64_t wk[W];              // per-wave best kept key and its local index
+  int wi[W];
+  uint64_t rkey;               // the pod's winning key, workgroup (-1 none), p, this workgroup's candidate
+  int rwg, rp, cand;
+  int abort;
+};
+
+template <uint32_t FM, uint32_t SM, int K, int B>
+__global__ __launch_bounds__(B) void k_cbatch(const DevState* __restrict__ stp, BatchArgs pa) {
+  const DevState& st = *stp;
+  constexpr int W = B / 64;
+  static_assert(K * W <= 64, "one wave scans the per-(slot, wave) counts");
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int G = gridDim.x, g = blockIdx.x;
+  if (g == pa.hold) return;  // KGPU_OPT_HOLD_GROUP: a workgroup that never became resident
+  const int N = st.N, KF = st.to_find, lo = g * pa.per;
+  __shared__ CutShared<K, B> sh;
+  constexpr bool kStream = K > 4;  // as k_batch: rows loaded from the node columns where a pod needs them
+  constexpr int KR = kStream ? 1 : K;
+  constexpr bool kRecip = (SM & kDefRes) != 0 && SM != kRuntime;
+  NodeRes r[KR];
+#pragma unroll
+  for (int j = 0; j < KR; ++j) {
+    const int loc = j * B + tid, n = lo + loc;
+    r[j] = NodeRes{};
+    if (!kStream && loc < pa.per && n < N) r[j] = load_row<kRecip>(st, n);
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  int s = gp(st.cut_state)[0] % N, last_p = 0;
+  bool done = true;
+  for (int i = 0; i < pa.count; ++i) {
+    if (i == pa.abort_at && g == 0 && tid == 0) __hip_atomic_store(pa.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const kgpu_pod_query q = *cp(st.queries + pa.first + i);
+    const int se = pa.cut_nofilt ? 0 : s;
+    uint64_t* row1 = pa.cgran + ((size_t)i * 2 + 0) * G;
+    uint64_t* row2 = pa.cgran + ((size_t)i * 2 + 1) * G;
+    // ---- round 1: filters and counts
+    uint32_t fbits = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int loc = j * B + tid, n = lo + loc;
+      uint32_t fs = 1u;
+      if (loc < pa.per && n < N) {
+        if constexpr (kStream) fs = run_filters<FM>(st, q, load_row<kRecip>(st, n), n);
+        else fs = run_filters<FM>(st, q, r[j], n);
+      }
+      const bool f = fs == 0;
+      const uint64_t bh = __ballot(f && n >= se), bl = __ballot(f && n < se);
+      if (f) fbits |= 1u << j;
+      if (lane == 0) {
+        sh.chi[j * W + wave] = __popcll(bh);
+        sh.clo[j * W + wave] = __popcll(bl);
+      }
+    }
+    if (tid == 0) sh.pown = -1;
+    __syncthreads();
+    if (wave == 0) {
+      const int ch = lane < K * W ? sh.chi[lane] : 0, cl = lane < K * W ? sh.clo[lane] : 0;
+      int xh = ch, xl = cl;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int th = __shfl_up(xh, d), tl = __shfl_up(xl, d);
+        if (lane >= d) {
+          xh += th;
+          xl += tl;
+        }
+      }
+      if (lane < K * W) {
+        sh.chi[lane] = xh - ch;
+        sh.clo[lane] = xl - cl;
+      }
+      const uint32_t HI = (uint32_t)__builtin_amdgcn_readlane(xh, 63), LO = (uint32_t)__builtin_amdgcn_readlane(xl, 63);
+      if (lane == 0) store_sc1(row1 + g, kGValid | ((uint64_t)HI << 20) | (uint64_t)LO);
+      uint32_t c4[4] = {0, 0, 0, 0};
+      const bool ok = G <= 64 ? poll_counts<1>(row1, G, g, pa.abort, c4) : poll_counts<4>(row1, G, g, pa.abort, c4);
+      if (lane == 0) {
+        sh.base_hi = (int)c4[0];
+        sh.base_lo = (int)c4[1];
+        sh.tot_hi = (int)c4[2];
+        sh.tot_lo = (int)c4[3];
+        sh.abort = ok ? 0 : 1;
+        if (!ok) __hip_atomic_fetch_or(pa.abort, i == 0 ? kAbortClean : kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __syncthreads();
+    if (sh.abort) {
+      done = false;
+      break;
+    }
+    // ---- ranks, the cut, scores of the kept nodes
+    const int base_hi = sh.base_hi, tot_hi = sh.tot_hi, base_lo = tot_hi + sh.base_lo, total = tot_hi + sh.tot_lo;
+    const uint64_t tk = pod_tie_key(st.seed, pa.seq0 + i);
+    const uint64_t below = (1ull << lane) - 1;
+    uint64_t best = 0;
+    int bidx = -1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int loc = j * B + tid, n = lo + loc;
+      const bool f = (fbits >> j) & 1u, hi = n >= se;
+      const uint64_t bh = __ballot(f && hi), bl = __ballot(f && !hi);
+      const int rank = hi ? base_hi + sh.chi[j * W + wave] + __popcll(bh & below) + 1
+                          : base_lo + sh.clo[j * W + wave] + __popcll(bl & below) + 1;
+      const bool kept = f && rank <= KF;
+      if (f && rank == KF + 1) sh.pown = hi ? n - se : n + N - se;
+      if (__ballot(kept) != 0) {
+        uint64_t key = 0;
+        if (kept) {
+          NodeEval e{0, 0, 0, 0};
+          if constexpr (kStream) run_scores<SM>(st, q, load_row<kRecip>(st, n), n, e, false);
+          else run_scores<SM>(st, q, r[j], n, e, false);
+          const int64_t tot = key_total<SM>(st, e.partial, e.taint, e.na);
+          key = ((uint64_t)(tot + 1) << 40) | rank40(tk, (uint64_t)(st.node_base + n), st.tie_mode);
+        }
+        if (key > best) {
+          best = key;
+          bidx = loc;
+        }
+      }
+    }
+    wave_argmax(best, bidx);
+    if (lane == 0) {
+      sh.wk[wave] = best;
+      sh.wi[wave] = bidx;
+    }
+    __syncthreads();
+    // ---- round 2: keys and p
+    if (wave == 0) {
+      uint64_t k = lane < W ? sh.wk[lane] : 0;
+      int ci = lane < W ? sh.wi[lane] : -1;
+      wave_argmax(k, ci);
+      if (lane == 0) {
+        if (sh.pown >= 0) store_sc1(pa.cpos + i, kGValid | (uint64_t)(uint32_t)sh.pown);
+        store_sc1(row2 + g, kGValid | k);
+      }
+      uint64_t wkey = 0;
+      int wg = -1;
+      bool ok = G <= 64 ? poll_row<1, false>(row2, G, pa.abort, kGValid, kGValid, wkey, wg)
+                        : poll_row<4, false>(row2, G, pa.abort, kGValid, kGValid, wkey, wg);
+      int p = N;
+      if (ok && total > KF) {
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+          const uint64_t v = load_sc1(pa.cpos + i);
+          if (v & kGValid) {
+            p = (int)(uint32_t)v;
+            break;
+          }
+          if (load_sc1(pa.abort) != 0 || __builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) {
+            ok = false;
+            break;
+          }
+        }
+      }
+      if (lane == 0) {
+        sh.rkey = wkey;
+        sh.rwg = wg;
+        sh.rp = p;
+        sh.cand = ci;
+        sh.abort = ok ? 0 : 1;
+        if (!ok) __hip_atomic_fetch_or(pa.abort, kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __syncthreads();
+    if (sh.abort) {
+      done = false;
+      break;
+    }
+    // ---- the winner assumes and writes the record (generic_scheduler.go:184-191: one feasible node is
+    // returned unscored); every workgroup advances the rotation
+    const int wg = sh.rwg, p = sh.rp, cand = sh.cand;
+    if (wg == g && pa.assume && tid == cand % B) {
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        if (j == cand / B) {
+          if constexpr (kStream) {
+            NodeRes t = load_res(st, lo + cand);
+            assume_row(st, q, t, lo + cand);
+          } else {
+            assume_row(st, q, r[j], lo + cand);
+          }
+          assume_counts(st, pa.first + i, lo + cand);
+        }
+    }
+    if (tid == 0 && (wg == g || (wg < 0 && g == 0))) {
+      kgpu_result res;
+      res.node = wg < 0 ? -1 : st.node_base + lo + cand;
+      res.feasible = min(total, KF);
+      res.evaluated = p;
+      res.scored = (wg >= 0 && res.feasible >= 2) ? 1 : 0;
+      res.score = res.scored ? (int64_t)(sh.rkey >> 40) - 1 : 0;
+      gp(st.results)[pa.first + i] = res;
+    }
+    s = (s + p) % N;
+    last_p = p;
+  }
+  if (done && g == 0 && tid == 0) {
+    gp(st.cut_state)[0] = s;
+    gp(st.cut_state)[1] = last_p;
+  }
+}
+
 // ---------------------------------------------------------------- topology pipeline
 // PodTopologySpread (podtopologyspread/{filtering,scoring}.go), InterPodAffinity
 // (interpodaffinity/{filtering,scoring}.go) and DefaultPodTopologySpread
@@ -4576,6 +4837,47 @@ int launch_batch(const DevState* st, const BatchArgs& a, int groups, int geo, in
   }
   hipLaunchKernelGGL(k_batch_fixup, dim3((a.count + 3) / 4), dim3(256), 0, (hipStream_t)stream, st, a, groups);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// cut mode: [profile spec][geometry], the geometry table of k_batch
+template <uint32_t FM, uint32_t SM>
+struct CutRow {
+  static constexpr BatchFn fn[kNumGeo] = {k_cbatch<FM, SM, 1, 64>,  k_cbatch<FM, SM, 1, 128>, k_cbatch<FM, SM, 1, 192>,
+                                          k_cbatch<FM, SM, 1, 448>, k_cbatch<FM, SM, 1, 960>, k_cbatch<FM, SM, 4, 512>,
+                                          k_cbatch<FM, SM, 8, 512>};
+};
+static const BatchFn* const kCutBatch[] = {
+    CutRow<kRuntime, kRuntime>::fn,
+    CutRow<kFitFM, kFitSM>::fn,
+    CutRow<kDefaultFM, kDefaultSM>::fn,
+    CutRow<kDefaultFM, kAutoscalerSM>::fn,
+};
+static_assert(sizeof(kCutBatch) / sizeof(kCutBatch[0]) == kNumSpecs, "one k_cbatch row per profile instantiation");
+
+int launch_cbatch(const DevState* st, const BatchArgs& a, int groups, int geo, int spec, bool coop, void* stream) {
+  spec = batch_row(spec);
+  if (geo < 0 || geo >= kNumGeo || !a.cgran || !a.cpos) return -1;
+  const BatchFn fn = kCutBatch[spec][geo];
+  const int threads = kGeo[geo].B;
+  static bool attr_set[kNumSpecs][kNumGeo] = {};
+  if (!attr_set[spec][geo]) {  // one workgroup per CU, as launch_batch
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kBatchLdsPad) != hipSuccess)
+      return -1;
+    attr_set[spec][geo] = true;
+  }
+  BatchArgs arg = a;
+  const DevState* sp = st;
+  void* args[] = {(void*)&sp, (void*)&arg};
+  if (!coop && grid_fits(reinterpret_cast<const void*>(fn), threads, (size_t)kBatchLdsPad, groups)) {
+    hipLaunchKernelGGL(fn, dim3(groups), dim3(threads), (unsigned)kBatchLdsPad, (hipStream_t)stream, sp, arg);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  arg.hold = -1;  // every workgroup of a cooperative launch is resident
+  return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(fn), dim3(groups), dim3(threads), args,
+                                    (unsigned)kBatchLdsPad, (hipStream_t)stream) == hipSuccess
+             ? 0
+             : -1;
 }
 
 int eval_blocks(int N) {
