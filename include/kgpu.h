@@ -689,17 +689,30 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * pods whose normalize maxima are constant go through one persistent launch of the cut-mode batch kernel
  * (k_cbatch, every k_batch geometry: two granule exchanges per pod, feasible counts then keys; DESIGN.md
  * 4.3.1); 0 = the per-pod cut pipeline (k_eval, k_cut, k_final) for every pod (A/B switch and parity twin).
- * Pods that need the normalize pass, topology pods, diagnostic and nominated cycles take the per-pod
- * pipeline either way; nextStartNodeIndex stays continuous across the two.  KGPU_OPT_HOLD_GROUP and
- * KGPU_OPT_ABORT_AT are honoured inside the cut-mode launch as in k_batch. */
+ * Pods that need the normalize pass without topology state, diagnostic and nominated cycles take the
+ * per-pod pipeline either way, topology pods follow KGPU_OPT_CUT_TOPO_PERSISTENT; nextStartNodeIndex stays
+ * continuous across all of them.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured inside the
+ * cut-mode launch as in k_batch. */
 #define KGPU_OPT_CUT_PERSISTENT 24
+/* KGPU_OPT_CUT_TOPO_PERSISTENT (25): 1 (default) = with percentageOfNodesToScore below 100, runs of topology
+ * pods in a batch go through one persistent launch of k_tbatch's cut-mode instantiation (every k_tbatch
+ * geometry and profile row, unsharded engines: three granule exchanges per pod -- feasible counts, the
+ * normalize statistics of the kept nodes, keys and the cut position); 0 = the per-pod
+ * topology pipeline (k_topo_*, k_cut, k_topo_reg) for every topology pod under a cut (A/B switch and
+ * parity twin).  Diagnostic (kgpu_schedule_one) and nominated cycles, KGPU_OPT_TOPO_PERSISTENT 0 and
+ * clusters with more than 64 node label keys keep the per-pod pipeline either way.  KGPU_OPT_HOLD_GROUP
+ * and KGPU_OPT_ABORT_AT are honoured as in k_tbatch; evaluation ahead (KGPU_OPT_TOPO_AHEAD) is off inside
+ * a cut-mode run. */
+#define KGPU_OPT_CUT_TOPO_PERSISTENT 25
 int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
 /* Engine counters: out[0] = calls issued again with a cooperative launch after a persistent run's
  * workgroups were not all resident before its first pod (KGPU_OPT_COOPERATIVE); out[1] = persistent
  * launches; out[2] = cooperative persistent launches; out[3] = k_class_init launches (pod classes met
  * for the first time, kgpu_prepare_pods); out[4] = whole pod-table uploads (the table is otherwise sent
  * incrementally); out[5] = pods resolved inside cut-mode persistent launches (KGPU_OPT_CUT_PERSISTENT;
- * they also count in out[1] and in kgpu_debug_instantiation's out[3]).  Returns how many counters exist. */
+ * they also count in out[1] and in kgpu_debug_instantiation's out[3]); out[6] = pods resolved inside
+ * cut-mode persistent topology launches (KGPU_OPT_CUT_TOPO_PERSISTENT; k_tbatch pods only, as out[5] counts
+ * k_cbatch pods only).  Returns how many counters exist. */
 int kgpu_debug_counters(const kgpu_ctx* ctx, int64_t* out, int32_t n);
 /* Pure host, no context: the geometry the engine would pick.  kernel 1 = k_batch, 2 = k_tbatch;
  * first = KGPU_OPT_*_GEO value.  Returns the geometry index (>= 0) and fills out[0..3] = threads per

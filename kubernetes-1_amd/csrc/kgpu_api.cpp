@@ -269,6 +269,8 @@ struct kgpu_ctx {
                                     // of it cooperative)
   int32_t hold_group = -1;          // KGPU_OPT_HOLD_GROUP test hook
   bool cut_persistent = true;       // KGPU_OPT_CUT_PERSISTENT
+  bool cut_topo_persistent = true;  // KGPU_OPT_CUT_TOPO_PERSISTENT
+  int64_t n_cut_topo_pods = 0;      // kgpu_debug_counters: pods resolved inside cut-mode persistent topology launches
   DevBuf cgran;                     // cut-mode persistent runs: count and key granules, position words
   int64_t n_cut_pods = 0;           // kgpu_debug_counters: pods resolved inside cut-mode persistent launches
   bool tbatch_wlab = true;          // KGPU_OPT_TBATCH_WLAB
@@ -1323,7 +1325,8 @@ size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kTMiscBytes = 1024;
 
 // LDS layout of a run (byte offsets into the dynamic region); returns the total
-size_t t_layout(const TRun& tr, kgpu::TBatchArgs* a, int B, int lab_keys = 0, int per = 0, size_t wlab_n = 0) {
+size_t t_layout(const TRun& tr, kgpu::TBatchArgs* a, int B, int lab_keys = 0, int per = 0, size_t wlab_n = 0,
+                bool cut = false) {
   size_t o = a16((size_t)tr.lds_bins * 4);
   const size_t o_reg = o;
   o = a16(o + (size_t)tr.reg_words * 4);
@@ -1342,6 +1345,8 @@ size_t t_layout(const TRun& tr, kgpu::TBatchArgs* a, int B, int lab_keys = 0, in
   o = a16(o + (size_t)std::max(tr.pt_max, 1) * 8);
   const size_t o_misc = o;
   o = a16(o + kTMiscBytes);
+  const size_t o_cut = o;  // cut mode's rank state
+  o = a16(o + (cut ? (size_t)kgpu::kTCutBytes : 0));
   const size_t o_lab = o;
   o = a16(o + (size_t)lab_keys * (size_t)per * 4);
   const size_t o_wlab = o;
@@ -1359,6 +1364,7 @@ size_t t_layout(const TRun& tr, kgpu::TBatchArgs* a, int B, int lab_keys = 0, in
     a->o_zsum = (int32_t)o_zsum;
     a->o_pt = (int32_t)o_pt;
     a->o_misc = (int32_t)o_misc;
+    a->o_cut = (int32_t)o_cut;
     a->R = R;
   }
   return o;
@@ -1594,7 +1600,7 @@ void t_finish(TRun& tr) {
 
 // Upload a planned run and launch k_tbatch_init + k_tbatch on the engine's stream.
 int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, int32_t assume, int per, int groups,
-               int geo, int32_t* abort_word, bool xg, bool diag) {
+               int geo, int32_t* abort_word, bool xg, bool diag, bool cut) {
   t_finish(tr);
   int rc;
   kgpu::TBatchArgs a{};
@@ -1622,11 +1628,11 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   // (a one-pod run reads each label it needs once: copying the workgroup's label values into LDS first
   // would only add a round of loads to its start)
   int lab_keys = count == 1 ? 0 : std::min(c->st.K, 16);
-  while (lab_keys > 0 && t_layout(tr, nullptr, 512, lab_keys, per) > (size_t)kgpu::kTLdsBudget) --lab_keys;
+  while (lab_keys > 0 && t_layout(tr, nullptr, 512, lab_keys, per, 0, cut) > (size_t)kgpu::kTLdsBudget) --lab_keys;
   // every node's label values of the delta keys, for the winner's (a batch run, when they fit too)
   size_t wlab_n = (count > 1 && !xg && c->st.K > 0 && c->tbatch_wlab) ? (size_t)c->st.K * (size_t)c->st.N : 0;
-  if (wlab_n && t_layout(tr, nullptr, 512, lab_keys, per, wlab_n) > (size_t)kgpu::kTLdsBudget) wlab_n = 0;
-  size_t lds = t_layout(tr, &a, 512, lab_keys, per, wlab_n);
+  if (wlab_n && t_layout(tr, nullptr, 512, lab_keys, per, wlab_n, cut) > (size_t)kgpu::kTLdsBudget) wlab_n = 0;
+  size_t lds = t_layout(tr, &a, 512, lab_keys, per, wlab_n, cut);
   // at least half a CU's LDS: one persistent workgroup per CU (two would share its SIMDs)
   a.lds_bytes = (int32_t)std::max<size_t>(lds, 96 * 1024);
   const size_t N = (size_t)c->st.N;
@@ -1712,11 +1718,13 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   a.hists = dh;
   a.sigs = dsg;
   a.regs = drg;
-  // zeroed region: hist_init | tot_init | reg_init | sig_any | elig | granules
+  // zeroed region: hist_init | tot_init | reg_init | sig_any | elig | granules (cut mode: one more row of
+  // count granules per pod, then the run's position words)
   const size_t b_hist = a16((size_t)std::max(tr.lds_bins, 1) * 4), b_tot = a16(std::max<size_t>(tr.hists.size(), 1) * 4);
   const size_t b_reg = a16((size_t)std::max(tr.reg_words, 1) * 4), b_sany = a16(std::max<size_t>(tr.sigs.size(), 1) * 4);
   const size_t b_elig = a16(std::max<size_t>(tr.sigs.size() * ew, 1) * 4);
-  const size_t b_gran = (size_t)count * (size_t)(a.R + 1) * (size_t)groups * 8;
+  const size_t b_cells = (size_t)count * (size_t)(a.R + (cut ? 2 : 1)) * (size_t)groups * 8;
+  const size_t b_gran = b_cells + (cut ? a16((size_t)count * 8) : 0);
   const size_t b_init = b_hist + b_tot + b_reg + b_sany + b_elig;
   char* zinit = nullptr;  // the init region in TCache's buffer (use_tc), else in the zeroed region
   int tc_use = 0;  // the TCache buffer this run uses; the other is zeroed by the kernel
@@ -1754,6 +1762,8 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   a.sig_any = reinterpret_cast<int32_t*>(zi + b_hist + b_tot + b_reg);
   a.elig = reinterpret_cast<uint32_t*>(zi + b_hist + b_tot + b_reg + b_sany);
   a.gran = reinterpret_cast<uint64_t*>(use_tc ? z : z + b_init);
+  a.cpos = cut ? reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.gran) + b_cells) : nullptr;
+  a.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
   a.writeback = use_tc ? 1 : 0;
   a.zero_n16 = 0;
   a.zero_buf = nullptr;
@@ -1824,7 +1834,8 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   ++c->state_launches;
   note_geometry(c, 2, geo, groups, per);
   note_instantiation(c, kgpu::tbatch_row(c->spec, a.def_res != 0), xg, false, count);
-  if (kgpu::launch_tbatch(dst, a, groups, geo, c->spec, xg, coop, c->stream))
+  if (cut) c->n_cut_topo_pods += count;
+  if (kgpu::launch_tbatch(dst, a, groups, geo, c->spec, xg, coop, c->stream, cut))
     return fail(c, KGPU_E_DEVICE, std::string("k_tbatch launch failed: ") + hipGetErrorString(hipGetLastError()));
   if (c->ar.on) ht(c, 7);  // 7: the launch (API call)
   if (use_tc) {
@@ -2273,6 +2284,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   };
   bool used_persistent = false;
   int64_t cut_pods = 0;  // this call's pods inside cut-mode runs (taken back when the call is issued again)
+  int64_t cut_topo_pods = 0;  // ... and inside cut-mode persistent topology runs
   int32_t* done_word = nullptr;  // the pinned completion word of the call's last kernel (one-pod cycles)
   // one abort word for every persistent run of this batch (OR-ed on the device)
   int rc_abort = ensure(c, c->abort_buf, 64);
@@ -2283,8 +2295,10 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   // instantiation); without them, the per-pod RCCL pipeline
   // a diagnostic cycle (kgpu_schedule_one: status words and per-plugin scores) of one topology pod
   // runs as a one-pod persistent run too
-  const int tgeo = (topo_on && c->tfast && (!diag || (n == 1 && !st.run_all)) && (!sharded || xg) && !cut && !nom_dev &&
-                    st.K <= 64)
+  // under a cut (percentageOfNodesToScore < 100) batch runs take its cut-mode instantiation
+  // (KGPU_OPT_CUT_TOPO_PERSISTENT); diagnostic cycles keep the per-pod pipeline (k_cut)
+  const int tgeo = (topo_on && c->tfast && (!diag || (n == 1 && !st.run_all)) && (!sharded || xg) &&
+                    (!cut || (c->cut_topo_persistent && !diag)) && !nom_dev && st.K <= 64)
                        ? kgpu::tbatch_geometry(st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
                                                &tper, &tgroups, c->tbatch_geo_first)
                        : -1;
@@ -2309,8 +2323,9 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       if (j > i) {
         if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
         if ((rc = run_tbatch(c, tr, i, j - i, first_seq, assume, tper, tgroups, tgeo, tb_arena ? nullptr : abort_word, xg,
-                             diag)))
+                             diag, cut)))
           return rc;
+        if (cut) cut_topo_pods += j - i;
         // the one-pod run's last workgroup copies the abort word into pinned memory after everything is
         // written back: the call's completion word
         done_word = (c->tb_abort_mapped && !c->timing && !c->phase_trace)
@@ -2642,6 +2657,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     c->tc.valid = false;
     for (int k = 0; k < 2; ++k) c->tc.dirty[k] = c->tc.buf[k].bytes;
     c->n_cut_pods -= cut_pods;
+    c->n_cut_topo_pods -= cut_topo_pods;
     return kCleanAbort;
   }
   c->port_bound += batch_ports;
@@ -3836,10 +3852,10 @@ int kgpu_read_phase_trace(kgpu_ctx* c, int64_t* out, int32_t max_pods) try {
 
 int kgpu_debug_counters(const kgpu_ctx* c, int64_t* out, int32_t n) {
   if (!c || (n > 0 && !out)) return KGPU_E_INVAL;
-  const int64_t v[6] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
-                        c->n_cut_pods};
-  for (int32_t i = 0; i < n && i < 6; ++i) out[i] = v[i];
-  return 6;
+  const int64_t v[7] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
+                        c->n_cut_pods, c->n_cut_topo_pods};
+  for (int32_t i = 0; i < n && i < 7; ++i) out[i] = v[i];
+  return 7;
 }
 
 int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]) try {
@@ -3927,6 +3943,7 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_RUN_ALL_FILTERS) c->run_all = value != 0;
   else if (option == KGPU_OPT_HOLD_GROUP) c->hold_group = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else if (option == KGPU_OPT_CUT_PERSISTENT) c->cut_persistent = value != 0;
+  else if (option == KGPU_OPT_CUT_TOPO_PERSISTENT) c->cut_topo_persistent = value != 0;
   else if (option == KGPU_OPT_SKIP_RELEASE_AT) c->skip_release_at = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else return KGPU_E_INVAL;
   return KGPU_OK;

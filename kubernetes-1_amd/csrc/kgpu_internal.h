@@ -324,6 +324,7 @@ constexpr int kXgmiMaxGT = 1024;     // granules per row the poll sweeps (16 per
 constexpr int kTMaxSoftWords = 8;   // shared ScheduleAnyway key: <= 256 domains (OR-ed bitmask)
 constexpr int kTMaxZones = 32;      // DefaultPodTopologySpread zone sums carried in the stats round
 constexpr int kTLdsBudget = 144 * 1024;
+constexpr int kTCutBytes = 544;     // cut mode's rank state in LDS (TCutShared, kgpu_kernels.hip)
 
 struct THist {
   int32_t col_kind;  // 0: mcnt pod class, 1: tcnt term class
@@ -415,7 +416,8 @@ struct TBatchArgs {
   uint32_t* reg_init;     // [reg_words]
   int32_t* sig_any;       // [n_sigs]
   uint32_t* elig;         // [n_sigs][ceil(N/32)]
-  uint64_t* gran;         // per pod: [R][groups] statistics granules, then [groups] key granules; zeroed
+  uint64_t* gran;         // per pod: [R][groups] statistics granules, then [groups] key granules (cut mode:
+                          // then [groups] count granules); zeroed
   int32_t* abort;
   int32_t* done;          // null, or a zeroed counter of workgroups that left the pod loop ...
   int32_t* abort_out;     // ... and the pinned host word the last of them copies the abort word into
@@ -459,6 +461,10 @@ struct TBatchArgs {
   uint64_t* const* ptx;   // [nranks] TX ring bases (this rank's own at [rank])
   int32_t nranks, rank;
   int64_t xseq0;
+  // ---- percentageOfNodesToScore < 100 (the CUT instantiation, unsharded engines; to_find is DevState's)
+  uint64_t* cpos;         // [count] position words: valid | p, published by the owner of rank to_find + 1; zeroed
+  int32_t cut_nofilt;     // the profile has no filter plugins: ranks in non-rotated order (as BatchArgs)
+  int32_t o_cut;          // LDS byte offset of the rank state (kTCutBytes)
 };
 
 // TX row of the topology mailbox ring, in u64 words: stats [nranks][kTXRCap] | keys [nranks] |
@@ -598,8 +604,9 @@ int64_t kernel_layout_sig();
 // k_tbatch_init over the local nodes (a.per * groups >= N); then, on a node-sharded
 // engine, launch_xreduce over the init region; then launch_tbatch (xg: the XG instantiation).
 int launch_tbatch_init(const DevState* st, const TBatchArgs& a, int groups, void* stream);
+// cut: the cut-mode instantiation (TBatchArgs.cpos / o_cut set, to_find < N; never with xg)
 int launch_tbatch(const DevState* st, const TBatchArgs& a, int groups, int geo, int spec, bool xg, bool coop,
-                  void* stream);
+                  void* stream, bool cut = false);
 // The k_tbatch profile row launch_tbatch indexes for `spec` and TBatchArgs.def_res (kgpu_debug_instantiation).
 int tbatch_row(int spec, bool def_res);
 

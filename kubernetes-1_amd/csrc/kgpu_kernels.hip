@@ -2191,6 +2191,17 @@ struct CutShared {
   int abort;
 };
 
+// The same ranks for k_tbatch's cut mode (in its dynamic LDS at TBatchArgs::o_cut; K * W <= 64)
+struct TCutShared {
+  int32_t chi[64], clo[64];    // feasible counts per (slot, wave), then their exclusive prefixes
+  int32_t base_hi, base_lo, tot_hi, tot_lo;
+  int32_t pown;                // p when this workgroup holds rank to_find + 1, else -1
+  int32_t rp;                  // the pod's p as every workgroup read it
+  int32_t s, total;            // nextStartNodeIndex before the pod; the cluster's feasible nodes before the cut
+                               // (kept here, not in registers: the kernel's register budget is its pct = 100 twin's)
+};
+static_assert(sizeof(TCutShared) <= kTCutBytes, "kTCutBytes (kgpu_internal.h) holds TCutShared");
+
 template <uint32_t FM, uint32_t SM, int K, int B>
 __global__ __launch_bounds__(B) void k_cbatch(const DevState* __restrict__ stp, BatchArgs pa) {
   const DevState& st = *stp;
@@ -3694,8 +3705,17 @@ __device__ __forceinline__ bool trow_topo(const DevState& st, const TBatchArgs& 
   return true;
 }
 
-template <int B, int K, uint32_t FM, uint32_t SM, bool kDef, bool XG>
+// CUT (percentageOfNodesToScore < 100, unsharded engines): a pod takes three granule
+// exchanges.  Round 0 is k_cbatch's counts round over the evaluated rows (valid | hi << 20 | lo, every
+// workgroup sums the row, ranks in rotated list order from ballots and the per-(slot, wave) prefixes in
+// TCutShared); rows of rank <= to_find are KEPT.  The statistics and key rounds then run over the kept rows
+// only, the owner of rank to_find + 1 publishes valid | p in the pod's position word with its key, and
+// every workgroup advances s by p.  s comes from cut_state at run start; workgroup 0 writes it back at
+// the end of a complete run.  No evaluation ahead in this mode.
+template <int B, int K, uint32_t FM, uint32_t SM, bool kDef, bool XG, bool CUT = false>
 __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, TBatchArgs ta) {
+  static_assert(!(CUT && XG), "a cut on a node-sharded engine is refused");
+  static_assert(!CUT || K * (B / 64) <= 64, "one wave scans the per-(slot, wave) counts");
   const DevState& st = *stp;
   __shared__ uint64_t* sh_ptx[XG ? kMaxRanks : 1];  // every rank's TX ring base (XG)
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -3891,7 +3911,7 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
   // Evaluation ahead (one row per lane): the next pod's non-topology filters and scores (trow_ind) run
   // while this pod's statistics round is in flight; the candidate lane evaluates them again on its row
   // with this pod applied while the key round is in flight, for the case its workgroup wins.
-  constexpr bool kAhead = K == 1;
+  constexpr bool kAhead = K == 1 && !CUT;
   // kDefer (diagnostic runs of a compile-time profile, one row per lane): the cycle's status word, raw
   // and normalized scores stay in registers until the pod is resolved, then every row of the lane's
   // node is stored once -- stores issued during the pod would hold every later load and the exchanges'
@@ -3905,6 +3925,9 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
   bool ind_ok = false, nx_ok = false, vb_ok = false;
   int log_guess = 2;                         // (uniform) math.Log index of the last pod's topology size
   TRow ind_o{}, nx_o{}, vb_o{};              // part / taint / na only
+  if constexpr (CUT) {  // nextStartNodeIndex (read by every thread after the pod loop's first barrier)
+    if (tid == 0) reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut)->s = gp(st.cut_state)[0] % st.N;
+  }
   if (trun) trun_row[1] = (int64_t)__builtin_amdgcn_s_memrealtime();
   for (int i = 0; i < ta.count; ++i) {
     KGPU_TSTAMP(0);
@@ -3995,6 +4018,7 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
         if (sw) continue;
       }
       feas[j] = true;
+      if constexpr (CUT) continue;  // the statistics are taken over the kept rows, after the counts round
       ++sf;
       smaxT = max(smaxT, (uint32_t)o[j].taint);
       smaxNA = max(smaxNA, (uint32_t)o[j].na);
@@ -4015,6 +4039,93 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
       if (z >= 0) {
         szoned = 1;
         if (o[j].ds && z < ta.zones) atomicAdd(ZSUM + z, o[j].ds);
+      }
+    }
+    if constexpr (CUT) {
+      // ---- round 0: feasible counts at or above s and below s, every workgroup sums the row (k_cbatch)
+      TCutShared& C = *reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut);
+      const int se = ta.cut_nofilt ? 0 : C.s, KF = st.to_find;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const int n = lo + j * B + tid;
+        const uint64_t bh = __ballot(feas[j] && n >= se), bl = __ballot(feas[j] && n < se);
+        if (lane == 0) {
+          C.chi[j * W + wave] = __popcll(bh);
+          C.clo[j * W + wave] = __popcll(bl);
+        }
+      }
+      if (tid == 0) C.pown = -1;
+      __syncthreads();
+      uint64_t* crow = ta.gran + ((size_t)i * (R + 2) + R + 1) * G;
+      if (wave == 0) {
+        const int ch = lane < K * W ? C.chi[lane] : 0, cl = lane < K * W ? C.clo[lane] : 0;
+        int xh = ch, xl = cl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int th = __shfl_up(xh, d), tl = __shfl_up(xl, d);
+          if (lane >= d) {
+            xh += th;
+            xl += tl;
+          }
+        }
+        if (lane < K * W) {
+          C.chi[lane] = xh - ch;
+          C.clo[lane] = xl - cl;
+        }
+        const uint32_t HI = (uint32_t)__builtin_amdgcn_readlane(xh, 63), LO = (uint32_t)__builtin_amdgcn_readlane(xl, 63);
+        if (lane == 0) store_sc1(crow + g, kGValid | ((uint64_t)HI << 20) | (uint64_t)LO);
+        uint32_t c4[4] = {0, 0, 0, 0};
+        const bool cok = G <= 64 ? poll_counts<1>(crow, G, g, ta.abort, c4) : poll_counts<4>(crow, G, g, ta.abort, c4);
+        if (lane == 0) {
+          C.base_hi = (int)c4[0];
+          C.base_lo = (int)c4[1];
+          C.tot_hi = (int)c4[2];
+          C.tot_lo = (int)c4[3];
+          C.total = (int)(c4[2] + c4[3]);
+          if (!cok) {  // pod 0's counts never came: no workgroup resolved a pod of this run
+            __hip_atomic_fetch_or(ta.abort, i == 0 ? kAbortClean : kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            M.abort = 1;
+          }
+        }
+      }
+      __syncthreads();
+      if (M.abort) break;
+      // ---- ranks in rotated list order and the cut; the statistics of the kept rows (as the pass above
+      // takes them over the feasible rows when nothing is cut)
+      const int base_hi = C.base_hi, tot_hi = C.tot_hi, base_lo = tot_hi + C.base_lo;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const int n = lo + j * B + tid;
+        const bool f = feas[j], hi = n >= se;
+        const uint64_t bh = __ballot(f && hi), bl = __ballot(f && !hi);
+        const uint64_t bm = hi ? bh : bl;  // feasible lanes below this one on its side of s
+        const int rank = (hi ? base_hi + C.chi[j * W + wave] : base_lo + C.clo[j * W + wave]) +
+                         (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) + 1;
+        if (f && rank == KF + 1) C.pown = hi ? n - se : n + st.N - se;
+        feas[j] = f && rank <= KF;
+        if (!feas[j]) continue;
+        ++sf;
+        smaxT = max(smaxT, (uint32_t)o[j].taint);
+        smaxNA = max(smaxNA, (uint32_t)o[j].na);
+        if (o[j].adj != INT64_MIN && tp.n_soft) {
+          ++snon;
+          sadjmin = min(sadjmin, (uint32_t)o[j].adj);
+          sadjmax = max(sadjmax, (uint32_t)o[j].adj);
+          if (tp.soft_mode == 0) {
+            const int v = tp.soft_key < ta.lab_keys ? LAB[tp.soft_key * ta.per + j * B + tid] : nval(st, tp.soft_key, n);
+            atomicOr(SMASK + (v >> 5), 1u << (v & 31));
+          }
+        }
+        simin = min(simin, o[j].ipa);
+        simax = max(simax, o[j].ipa);
+        sdmax = max(sdmax, (uint32_t)o[j].ds);
+        int z;
+        if constexpr (kStream) z = zone[j];
+        else z = sr[j].zone;
+        if (z >= 0) {
+          szoned = 1;
+          if (o[j].ds && z < ta.zones) atomicAdd(ZSUM + z, o[j].ds);
+        }
       }
     }
     if (ta.trace_mode < 2) KGPU_TSTAMP(2);
@@ -4056,7 +4167,8 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     }
     __syncthreads();
     KGPU_WSTAMP(4);
-    uint64_t* srow = ta.gran + (size_t)i * (R + 1) * G;  // [R][G] statistics granules | [G] keys
+    // [R][G] statistics granules | [G] keys (CUT: | [G] counts)
+    uint64_t* srow = ta.gran + (size_t)i * (R + (CUT ? 2 : 1)) * G;
     // one slot per thread.  Every thread reads its candidate words first -- clamped addresses, one LDS
     // round trip -- and then selects: a switch over the slot puts an LDS read and its wait in each of a
     // dozen divergent branches, which the wave runs one after another (0.7 us per pod).  The selection is
@@ -4294,6 +4406,10 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     wg_best(bkey0, bidx0, bk, bi);
     if (ta.trace_mode == 2) KGPU_TSTAMP(2);  // ... and the workgroup's best key known
     if (wave == 0 && lane == 0) store_sc1(arow + g, kGValid | bk);
+    if constexpr (CUT) {  // the owner of rank to_find + 1 publishes p (nobody when total <= to_find: p = N)
+      const int pown = reinterpret_cast<const TCutShared*>(lds_raw + ta.o_cut)->pown;
+      if (wave == 0 && lane == 0 && pown >= 0) store_sc1(ta.cpos + i, kGValid | (uint64_t)(uint32_t)pown);
+    }
     // the candidate row with this pod applied, for the next pod (used when this workgroup wins; a pod
     // with host ports or extended resources changes memory columns: its winner is evaluated again
     // after the assume instead)
@@ -4309,6 +4425,24 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
       uint64_t wkey = 0;
       int wg = -1;
       bool pok = poll_row<4, false>(arow, G, ta.abort, kGValid, kGValid, wkey, wg);
+      if constexpr (CUT) {
+        int p = st.N;
+        if (pok && reinterpret_cast<const TCutShared*>(lds_raw + ta.o_cut)->total > st.to_find) {
+          const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+          for (;;) {
+            const uint64_t v = load_sc1(ta.cpos + i);
+            if (v & kGValid) {
+              p = (int)(uint32_t)v;
+              break;
+            }
+            if (load_sc1(ta.abort) != 0 || __builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) {
+              pok = false;  // dirty, as a key-poll timeout (below)
+              break;
+            }
+          }
+        }
+        if (lane == 0) reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut)->rp = p;
+      }
       if constexpr (XG) {
         // this rank's best: its local winner publishes the record -- the winning node's label values
         // and signature bits first, then (after a system-scope release) the key; workgroup 0 publishes
@@ -4395,9 +4529,14 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
       res.node = placed ? wnode : (error ? -2 : -1);
       res.feasible = (int32_t)feas_total;
       res.evaluated = st.n_total;
+      if constexpr (CUT) res.evaluated = reinterpret_cast<const TCutShared*>(lds_raw + ta.o_cut)->rp;
       res.scored = (placed && feas_total >= 2) ? 1 : 0;
       res.score = res.scored ? (int64_t)(M.wkey >> 40) - 1 : 0;
       gp(st.results)[pod] = res;
+    }
+    if constexpr (CUT) {  // every workgroup advances the rotation (read again after the pod's last barrier)
+      TCutShared& C = *reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut);
+      if (tid == 0) C.s = (C.s + C.rp) % st.N;
     }
     if (placed && ta.assume) {
       const int wl = wnode - st.node_base;
@@ -4485,6 +4624,14 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
   if (ta.writeback && g == 0 && !M.abort) {
     for (int b = tid; b < ta.lds_bins; b += B) gp(ta.hist_init)[b] = H[b];
     for (int h = tid; h < ta.n_hists; h += B) gp(ta.tot_init)[h] = TOT[h];
+  }
+  if constexpr (CUT) {
+    // the rotation continues in the next launch of any kind; an aborted run leaves it
+    const TCutShared& C = *reinterpret_cast<const TCutShared*>(lds_raw + ta.o_cut);
+    if (g == 0 && tid == 0 && !M.abort) {  // (thread 0 wrote both)
+      gp(st.cut_state)[0] = C.s;
+      gp(st.cut_state)[1] = ta.count > 0 ? C.rp : 0;
+    }
   }
   if (trun) trun_row[2] = (int64_t)__builtin_amdgcn_s_memrealtime();
   leave();
@@ -4580,11 +4727,12 @@ struct TGeo {
 constexpr TGeo kTGeo[] = {{256, 1}, {512, 1}, {512, 2}, {512, 4}, {512, 8}};
 constexpr int kNumTGeo = sizeof(kTGeo) / sizeof(kTGeo[0]);
 using TBatchFn = void (*)(const DevState*, TBatchArgs);
-template <uint32_t FM, uint32_t SM, bool kDef, bool XG>
+template <uint32_t FM, uint32_t SM, bool kDef, bool XG, bool CUT = false>
 struct TBatchRow {
-  static constexpr TBatchFn fn[kNumTGeo] = {k_tbatch<256, 1, FM, SM, kDef, XG>, k_tbatch<512, 1, FM, SM, kDef, XG>,
-                                            k_tbatch<512, 2, FM, SM, kDef, XG>, k_tbatch<512, 4, FM, SM, kDef, XG>,
-                                            k_tbatch<512, 8, FM, SM, kDef, XG>};
+  static constexpr TBatchFn fn[kNumTGeo] = {
+      k_tbatch<256, 1, FM, SM, kDef, XG, CUT>, k_tbatch<512, 1, FM, SM, kDef, XG, CUT>,
+      k_tbatch<512, 2, FM, SM, kDef, XG, CUT>, k_tbatch<512, 4, FM, SM, kDef, XG, CUT>,
+      k_tbatch<512, 8, FM, SM, kDef, XG, CUT>};
 };
 // rows: 0 generic, 1 generic with Least/Most over {cpu:1, memory:1}, 2 default provider,
 // 3 ClusterAutoscaler provider; [1]: the node-sharded (xGMI) instantiations
@@ -4593,6 +4741,10 @@ static const TBatchFn* const kTBatch[2][4] = {
      TBatchRow<kDefaultFM, kDefaultSM, true, false>::fn, TBatchRow<kDefaultFM, kAutoscalerSM, true, false>::fn},
     {TBatchRow<kRuntime, kRuntime, false, true>::fn, TBatchRow<kRuntime, kRuntime, true, true>::fn,
      TBatchRow<kDefaultFM, kDefaultSM, true, true>::fn, TBatchRow<kDefaultFM, kAutoscalerSM, true, true>::fn}};
+// the cut-mode instantiations (percentageOfNodesToScore < 100): unsharded engines only, the same rows
+static const TBatchFn* const kCutTBatch[4] = {
+    TBatchRow<kRuntime, kRuntime, false, false, true>::fn, TBatchRow<kRuntime, kRuntime, true, false, true>::fn,
+    TBatchRow<kDefaultFM, kDefaultSM, true, false, true>::fn, TBatchRow<kDefaultFM, kAutoscalerSM, true, false, true>::fn};
 
 int64_t kernel_layout_sig() { return layout_sig_of(); }
 
@@ -4646,17 +4798,17 @@ int tbatch_row(int spec, bool def_res) { return spec == 2 ? 2 : (spec == 3 ? 3 :
 
 // spec: the k_eval profile instantiation (select_spec), def_res from the TBatchArgs
 int launch_tbatch(const DevState* st, const TBatchArgs& a, int groups, int geo, int spec, bool xg, bool coop,
-                  void* stream) {
-  if (geo < 0 || geo >= kNumTGeo) return -1;
+                  void* stream, bool cut) {
+  if (geo < 0 || geo >= kNumTGeo || (cut && xg)) return -1;
   hipStream_t s = (hipStream_t)stream;
   const int row = tbatch_row(spec, a.def_res != 0);
-  const TBatchFn fn = kTBatch[xg ? 1 : 0][row][geo];
-  static bool attr[2][4][kNumTGeo] = {};
-  if (!attr[xg ? 1 : 0][row][geo]) {
+  const TBatchFn fn = cut ? kCutTBatch[row][geo] : kTBatch[xg ? 1 : 0][row][geo];
+  static bool attr[3][4][kNumTGeo] = {};
+  if (!attr[cut ? 2 : (xg ? 1 : 0)][row][geo]) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kTLdsBudget) != hipSuccess)
       return -1;
-    attr[xg ? 1 : 0][row][geo] = true;
+    attr[cut ? 2 : (xg ? 1 : 0)][row][geo] = true;
   }
   // one workgroup per CU (>= 80 KB of LDS each); the cooperative launch checks co-residency
   TBatchArgs arg = a;
