@@ -689,9 +689,10 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * pods whose normalize maxima are constant go through one persistent launch of the cut-mode batch kernel
  * (k_cbatch, every k_batch geometry: two granule exchanges per pod, feasible counts then keys; DESIGN.md
  * 4.3.1); 0 = the per-pod cut pipeline (k_eval, k_cut, k_final) for every pod (A/B switch and parity twin).
- * Pods that need the normalize pass without topology state, diagnostic and nominated cycles take the
- * per-pod pipeline either way, topology pods follow KGPU_OPT_CUT_TOPO_PERSISTENT; nextStartNodeIndex stays
- * continuous across all of them.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured inside the
+ * Diagnostic and nominated cycles take the per-pod pipeline either way, topology pods follow
+ * KGPU_OPT_CUT_TOPO_PERSISTENT, pods that need the normalize pass without topology state follow
+ * KGPU_OPT_NORM_PERSISTENT (off by default: the per-pod pipeline); nextStartNodeIndex stays continuous
+ * across all of them.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured inside the
  * cut-mode launch as in k_batch. */
 #define KGPU_OPT_CUT_PERSISTENT 24
 /* KGPU_OPT_CUT_TOPO_PERSISTENT (25): 1 (default) = with percentageOfNodesToScore below 100, runs of topology
@@ -704,6 +705,21 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * and KGPU_OPT_ABORT_AT are honoured as in k_tbatch; evaluation ahead (KGPU_OPT_TOPO_AHEAD) is off inside
  * a cut-mode run. */
 #define KGPU_OPT_CUT_TOPO_PERSISTENT 25
+/* KGPU_OPT_NORM_PERSISTENT (26): 0 (default) = pods that need the normalize pass (a preferred node-affinity
+ * term, or a PreferNoSchedule taint in the cluster that the pod does not tolerate) and carry no topology
+ * state take the per-pod pipeline (k_eval, k_cut under a cut, k_final); v >= 1 = a batch's runs of them go
+ * through one persistent launch of k_nbatch (every k_batch geometry, the profile rows with a normalized
+ * plugin, pct = 100 and below: two granule exchanges per pod -- the two normalize maxima and the feasible
+ * count, then keys -- and under a cut the feasible counts before them).  A run starts at
+ * such a pod and extends over the following pods without topology state; a pod with constant maxima is
+ * evaluated by the same kernel (exactly) only while another normalize-pass pod lies within the next v - 1
+ * pods, so 1 takes normalize-pass pods only and a larger value trades k_batch's cheaper pods for fewer
+ * launches.  Diagnostic and nominated cycles, node-sharded engines, pods whose scoring fails,
+ * KGPU_OPT_PERSISTENT 0 (under a cut also KGPU_OPT_CUT_PERSISTENT 0), a cluster too large for the geometry
+ * table or with 16,384 or more taint words keep the per-pod pipeline either way; pipelined submits still
+ * refuse these pods.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured inside the launch as in
+ * k_cbatch; nextStartNodeIndex stays continuous with every other path. */
+#define KGPU_OPT_NORM_PERSISTENT 26
 int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
 /* Engine counters: out[0] = calls issued again with a cooperative launch after a persistent run's
  * workgroups were not all resident before its first pod (KGPU_OPT_COOPERATIVE); out[1] = persistent
@@ -712,7 +728,9 @@ int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
  * incrementally); out[5] = pods resolved inside cut-mode persistent launches (KGPU_OPT_CUT_PERSISTENT;
  * they also count in out[1] and in kgpu_debug_instantiation's out[3]); out[6] = pods resolved inside
  * cut-mode persistent topology launches (KGPU_OPT_CUT_TOPO_PERSISTENT; k_tbatch pods only, as out[5] counts
- * k_cbatch pods only).  Returns how many counters exist. */
+ * k_cbatch pods only); out[7] = pods resolved inside normalize-pass persistent launches
+ * (KGPU_OPT_NORM_PERSISTENT; k_nbatch pods, at pct = 100 and under a cut; they also count in out[1] and in
+ * kgpu_debug_instantiation's out[3], not in out[5]).  Returns how many counters exist. */
 int kgpu_debug_counters(const kgpu_ctx* ctx, int64_t* out, int32_t n);
 /* Pure host, no context: the geometry the engine would pick.  kernel 1 = k_batch, 2 = k_tbatch;
  * first = KGPU_OPT_*_GEO value.  Returns the geometry index (>= 0) and fills out[0..3] = threads per

@@ -270,6 +270,8 @@ struct kgpu_ctx {
   int32_t hold_group = -1;          // KGPU_OPT_HOLD_GROUP test hook
   bool cut_persistent = true;       // KGPU_OPT_CUT_PERSISTENT
   bool cut_topo_persistent = true;  // KGPU_OPT_CUT_TOPO_PERSISTENT
+  int32_t norm_persistent = 0;      // KGPU_OPT_NORM_PERSISTENT: 0 off, v >= 1 the absorb window of a k_nbatch run
+  int64_t n_norm_pods = 0;          // kgpu_debug_counters: pods resolved inside k_nbatch launches
   int64_t n_cut_topo_pods = 0;      // kgpu_debug_counters: pods resolved inside cut-mode persistent topology launches
   DevBuf cgran;                     // cut-mode persistent runs: count and key granules, position words
   int64_t n_cut_pods = 0;           // kgpu_debug_counters: pods resolved inside cut-mode persistent launches
@@ -2285,6 +2287,17 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   bool used_persistent = false;
   int64_t cut_pods = 0;  // this call's pods inside cut-mode runs (taken back when the call is issued again)
   int64_t cut_topo_pods = 0;  // ... and inside cut-mode persistent topology runs
+  int64_t norm_pods = 0;      // ... and inside normalize-pass persistent runs (k_nbatch)
+  // KGPU_OPT_NORM_PERSISTENT: pods that need the normalize pass and carry no topology state go through
+  // k_nbatch (unsharded batch runs; the profile row must hold a normalized plugin and the raw taint maximum,
+  // at most 64 per taint word, must fit the statistics granule's field)
+  std::vector<uint8_t> nrm;
+  if (c->norm_persistent > 0 && kidx >= 0 && !sharded && !diag && !nom_dev && kgpu::nbatch_row_ok(c->spec) &&
+      64 * (int64_t)std::max(st.TW, 0) < ((int64_t)1 << kgpu::kNormTaintBits)) {
+    nrm.assign((size_t)n, 0);
+    for (int32_t k = 0; k < n; ++k)
+      nrm[(size_t)k] = (!(qs[k].flags & KGPU_Q_SCORE_ERROR) && !topo[(size_t)k] && needs_norm(c, qs[k], pools)) ? 1 : 0;
+  }
   int32_t* done_word = nullptr;  // the pinned completion word of the call's last kernel (one-pod cycles)
   // one abort word for every persistent run of this batch (OR-ed on the device)
   int rc_abort = ensure(c, c->abort_buf, 64);
@@ -2427,7 +2440,60 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       i = i + 1;
       continue;
     }
-    if (kidx >= 0 && !norm[(size_t)i]) {
+    if (!nrm.empty() && nrm[(size_t)i]) {
+      // a run that starts at a normalize-pass pod: one persistent launch of k_nbatch.  It extends over the
+      // following non-topology pods; a constant-maxima pod is absorbed (exact: its maxima come out 0) only
+      // while another normalize-pass pod lies within the next norm_persistent - 1 pods.  The granule area
+      // is capped at 64 MiB: a longer run continues in another launch (under a cut from cut_state).
+      const size_t rounds = cut ? 3 : 2;
+      const int32_t max_run = (int32_t)std::max<size_t>(1, ((size_t)64 << 20) / (8 * rounds * (size_t)groups + 8));
+      auto plain = [&](int32_t k) { return !topo[(size_t)k] && (nrm[(size_t)k] || !norm[(size_t)k]); };
+      while (j < n && j - i < max_run && plain(j)) {
+        if (!nrm[(size_t)j]) {
+          bool near = false;
+          for (int32_t k = j + 1; k < n && k - j < c->norm_persistent && plain(k) && !near; ++k) near = nrm[(size_t)k] != 0;
+          if (!near) break;
+        }
+        ++j;
+      }
+      const int32_t cnt = j - i;
+      kgpu::BatchArgs ba{};
+      // layout: granules [cnt][rounds][groups] u64 | position words [cnt] u64 (read under a cut only), all zeroed
+      const size_t cells = (size_t)cnt * rounds * (size_t)groups;
+      const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
+      if ((rc = ensure(c, c->cgran, gbytes))) return rc;
+      HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
+      ba.cgran = static_cast<uint64_t*>(c->cgran.p);
+      ba.cpos = ba.cgran + cells;
+      ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
+      ba.nranks = 1;
+      ba.GT = groups;
+      ba.first = i;
+      ba.count = cnt;
+      ba.per = per;
+      ba.assume = assume;
+      ba.seq0 = first_seq + i;
+      ba.abort = abort_word;
+      ba.abort_at = c->abort_at >= i && c->abort_at < i + cnt ? c->abort_at - i : -1;
+      ba.skip_release_at = -1;
+      ba.trace = nullptr;
+      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
+      const bool coop = c->coop || c->force_coop;
+      ba.hold = coop ? -1 : c->hold_group;
+      ++c->n_persist;
+      c->n_coop += coop ? 1 : 0;
+      ++c->state_launches;
+      note_geometry(c, 1, kidx, groups, per);
+      note_instantiation(c, kgpu::batch_row(c->spec), false, false, cnt);
+      c->n_norm_pods += cnt;
+      norm_pods += cnt;
+      if (kgpu::launch_nbatch(dst, ba, groups, kidx, c->spec, coop, c->stream))
+        return fail(c, KGPU_E_DEVICE, "k_nbatch launch failed");
+      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
+      ev += 2;
+      timed_passes += cnt;
+      used_persistent = true;
+    } else if (kidx >= 0 && !norm[(size_t)i]) {
       // a run of pods with constant normalize maxima: one persistent launch
       // (a cut run's granule area is capped at 64 MiB: a longer run continues in another launch, which
       // takes up the rotation from cut_state)
@@ -2517,7 +2583,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
       used_persistent = true;
     } else {
       // one launch per pod; the next launch resolves (and assumes) the previous pod's winner
-      while (j < n && (kidx < 0 || norm[(size_t)j]) && !topo[(size_t)j]) ++j;
+      while (j < n && (kidx < 0 || norm[(size_t)j]) && !topo[(size_t)j] && (nrm.empty() || !nrm[(size_t)j])) ++j;
       int prev = -1;
       bool resolved_in_final = false;
       for (int32_t k = i; k < j; ++k) {
@@ -2658,6 +2724,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     for (int k = 0; k < 2; ++k) c->tc.dirty[k] = c->tc.buf[k].bytes;
     c->n_cut_pods -= cut_pods;
     c->n_cut_topo_pods -= cut_topo_pods;
+    c->n_norm_pods -= norm_pods;
     return kCleanAbort;
   }
   c->port_bound += batch_ports;
@@ -3852,10 +3919,10 @@ int kgpu_read_phase_trace(kgpu_ctx* c, int64_t* out, int32_t max_pods) try {
 
 int kgpu_debug_counters(const kgpu_ctx* c, int64_t* out, int32_t n) {
   if (!c || (n > 0 && !out)) return KGPU_E_INVAL;
-  const int64_t v[7] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
-                        c->n_cut_pods, c->n_cut_topo_pods};
-  for (int32_t i = 0; i < n && i < 7; ++i) out[i] = v[i];
-  return 7;
+  const int64_t v[8] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
+                        c->n_cut_pods, c->n_cut_topo_pods, c->n_norm_pods};
+  for (int32_t i = 0; i < n && i < 8; ++i) out[i] = v[i];
+  return 8;
 }
 
 int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]) try {
@@ -3944,6 +4011,7 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_HOLD_GROUP) c->hold_group = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else if (option == KGPU_OPT_CUT_PERSISTENT) c->cut_persistent = value != 0;
   else if (option == KGPU_OPT_CUT_TOPO_PERSISTENT) c->cut_topo_persistent = value != 0;
+  else if (option == KGPU_OPT_NORM_PERSISTENT) c->norm_persistent = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), INT32_MAX);
   else if (option == KGPU_OPT_SKIP_RELEASE_AT) c->skip_release_at = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else return KGPU_E_INVAL;
   return KGPU_OK;

@@ -570,6 +570,17 @@ int batch_row(int spec);
 // k_batch_fixup.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured as in k_batch.
 int launch_cbatch(const DevState* st, const BatchArgs& a, int groups, int kidx, int spec, bool coop, void* stream);
 bool batch_helper_used(int spec, int geo, bool sharded, bool helper);
+// The normalize-pass sibling (k_nbatch: pods whose DefaultNormalizeScore maxima are not constant, no topology
+// state; KGPU_OPT_NORM_PERSISTENT) on the same geometry table, for the profile rows that contain a normalized
+// plugin (the Fit row has none: refused).  BatchArgs.cgran: [count][2][groups] granules (statistics, keys) at
+// pct = 100, [count][3][groups] (counts, statistics, keys) plus cpos [count] under a cut, zeroed.  The kernel
+// writes every field of a pod's record: no k_batch_fixup.
+int launch_nbatch(const DevState* st, const BatchArgs& a, int groups, int kidx, int spec, bool coop, void* stream);
+// k_nbatch's statistics granule holds the raw TaintToleration maximum (at most 64 x taint words) in this many
+// bits; a cluster outside it stays on the per-pod path
+constexpr int kNormTaintBits = 20;
+// whether profile row `spec` has a k_nbatch instantiation
+bool nbatch_row_ok(int spec);
 // Topology pipeline for one pod (PodArgs.pod): domain histograms, critical-path minima, filters,
 // scores, normalize + argmax, resolve + assume.  next_scratch: words of the next topology pod's
 // scratch to zero in the resolve launch (0 none).

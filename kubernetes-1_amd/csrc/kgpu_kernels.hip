@@ -2396,6 +2396,343 @@ __global__ __launch_bounds__(B) void k_cbatch(const DevState* __restrict__ stp, 
   }
 }
 
+// ---------------------------------------------------------------- persistent batch kernel, normalize pass
+// k_cbatch's sibling for pods whose DefaultNormalizeScore maxima are not constant (a preferred node-affinity
+// term, an untolerated PreferNoSchedule taint) and that carry no topology state: a run of pods in ONE
+// launch on k_batch's geometry table, B row threads, no communication wave, no spare row.  The maxima are
+// taken over the pod's feasible nodes -- under percentageOfNodesToScore < 100 over the KEPT nodes -- so a
+// pod takes one exchange more than its constant-maxima twin:
+//   pct = 100 (cut_state null)   statistics, keys
+//   under a cut                  counts (k_cbatch's round 1 as it stands), statistics, keys + position word
+// The cut is a uniform per-run flag, not a template parameter: the counts round is skipped by a scalar
+// branch, and the translation unit compiles 21 instantiations instead of 42.
+//   statistics  valid | max_taint << 43 | max_na << 12 | feasible: the workgroup's maxima of the raw
+//               TaintToleration and NodeAffinity scores over its feasible (kept) rows and their number;
+//               every workgroup polls the complete row and takes the sum and the two maxima.
+//   keys        valid | ((norm_total + 1) << 40 | rank40), norm_total being k_final's function.
+// The winning workgroup assumes and writes the whole record (no fixup launch): at pct = 100 FeasibleNodes
+// is the statistics' sum and EvaluatedNodes n_total, as k_batch + k_batch_fixup write them; under a cut
+// they are min(total, to_find) and p, as k_cbatch writes them.  A pod whose maxima are constant comes
+// out with both 0, and norm_total(.., 0, 0) is key_total: such a pod inside a run is exact.
+// The resident geometries (K <= 4) keep partial / taint / na of their rows across the statistics exchange;
+// the streamed one (K = 8) reloads its rows anyway and runs the scores again in the key pass.
+// Aborts: a poll that outlives kSpinTimeout before the key round of the run's first pod raises kAbortClean
+// (nobody can have resolved a pod); every key-round or position-word timeout and every later one is dirty.
+constexpr int kNStatFeasBits = 12, kNStatNaBits = 31, kNStatTaintBits = 20;
+static_assert(kNStatFeasBits + kNStatNaBits + kNStatTaintBits == 63, "the statistics granule: 63 bits under the valid bit");
+static_assert(kNStatTaintBits == kNormTaintBits, "the host keeps clusters outside the taint field on the per-pod path");
+
+template <int NJ>
+__device__ __forceinline__ bool poll_stats(const uint64_t* row, int G, const int32_t* abort_word, uint32_t (&out)[3]) {
+  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+  for (;;) {
+    const Sweep<NJ> a = sweep<NJ, false>(row, G, abort_word, kGValid);
+    if (__any(a.abort != 0)) return false;
+    bool all = true;
+    uint32_t f = 0, mt = 0, mn = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const uint64_t v = a.v[j];
+      if (!(v & kGValid)) all = false;
+      f += (uint32_t)v & ((1u << kNStatFeasBits) - 1);
+      mn = max(mn, (uint32_t)(v >> kNStatFeasBits) & 0x7FFFFFFFu);
+      mt = max(mt, (uint32_t)(v >> (kNStatFeasBits + kNStatNaBits)) & ((1u << kNStatTaintBits) - 1));
+    }
+    if (__all(all)) {
+      out[0] = wave_sum32(f);
+      out[1] = wave_max32u(mt);
+      out[2] = wave_max32u(mn);
+      return true;
+    }
+    if (__builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) return false;
+  }
+}
+
+template <int K, int B>
+struct NormShared {
+  static constexpr int W = B / 64;
+  CutShared<K, B> c;
+  int wt[W], wn[W], wf[W];  // per-wave maxima of the raw taint / node-affinity scores, feasible (kept) rows
+  int maxT, maxNA, feas;    // the pod's statistics as every workgroup read them
+};
+
+template <uint32_t FM, uint32_t SM, int K, int B>
+__global__ __launch_bounds__(B) void k_nbatch(const DevState* __restrict__ stp, BatchArgs pa) {
+  const DevState& st = *stp;
+  constexpr int W = B / 64;
+  static_assert(K * W <= 64, "one wave scans the per-(slot, wave) counts");
+  static_assert(K * B - 1 < (1 << kNStatFeasBits), "a workgroup's feasible count fits the statistics granule");
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int G = gridDim.x, g = blockIdx.x;
+  if (g == pa.hold) return;  // KGPU_OPT_HOLD_GROUP: a workgroup that never became resident
+  const int N = st.N, KF = st.to_find, lo = g * pa.per;
+  const bool cut = st.cut_state != nullptr;  // uniform for the run
+  const int R = cut ? 3 : 2;
+  __shared__ NormShared<K, B> nsh;
+  CutShared<K, B>& sh = nsh.c;
+  constexpr bool kStream = K > 4;
+  constexpr int KR = kStream ? 1 : K;
+  constexpr bool kRecip = (SM & kDefRes) != 0 && SM != kRuntime;
+  NodeRes r[KR];
+  int64_t ep[KR];  // resident geometries: the rows' scores, kept across the statistics exchange
+  int et[KR], en[KR];
+#pragma unroll
+  for (int j = 0; j < KR; ++j) {
+    const int loc = j * B + tid, n = lo + loc;
+    r[j] = NodeRes{};
+    ep[j] = 0;
+    et[j] = en[j] = 0;
+    if (!kStream && loc < pa.per && n < N) r[j] = load_row<kRecip>(st, n);
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  int s = cut ? gp(st.cut_state)[0] % N : 0, last_p = 0;
+  bool done = true;
+  for (int i = 0; i < pa.count; ++i) {
+    if (i == pa.abort_at && g == 0 && tid == 0) __hip_atomic_store(pa.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const kgpu_pod_query q = *cp(st.queries + pa.first + i);
+    const int se = (!cut || pa.cut_nofilt) ? 0 : s;
+    uint64_t* rowc = pa.cgran + (size_t)i * R * G;  // counts (cut only)
+    uint64_t* rows = rowc + (cut ? G : 0);            // statistics
+    uint64_t* rowk = rows + G;                        // keys
+    // ---- filters (and, under a cut, round 1: counts)
+    uint32_t fbits = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int loc = j * B + tid, n = lo + loc;
+      uint32_t fs = 1u;
+      if (loc < pa.per && n < N) {
+        if constexpr (kStream) fs = run_filters<FM>(st, q, load_row<kRecip>(st, n), n);
+        else fs = run_filters<FM>(st, q, r[j], n);
+      }
+      const bool f = fs == 0;
+      if (f) fbits |= 1u << j;
+      if (cut) {
+        const uint64_t bh = __ballot(f && n >= se), bl = __ballot(f && n < se);
+        if (lane == 0) {
+          sh.chi[j * W + wave] = __popcll(bh);
+          sh.clo[j * W + wave] = __popcll(bl);
+        }
+      }
+    }
+    uint32_t kbits = fbits;  // the rows the maxima and the keys run over
+    int total = 0;
+    if (cut) {
+      if (tid == 0) sh.pown = -1;
+      __syncthreads();
+      if (wave == 0) {
+        const int ch = lane < K * W ? sh.chi[lane] : 0, cl = lane < K * W ? sh.clo[lane] : 0;
+        int xh = ch, xl = cl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int th = __shfl_up(xh, d), tl = __shfl_up(xl, d);
+          if (lane >= d) {
+            xh += th;
+            xl += tl;
+          }
+        }
+        if (lane < K * W) {
+          sh.chi[lane] = xh - ch;
+          sh.clo[lane] = xl - cl;
+        }
+        const uint32_t HI = (uint32_t)__builtin_amdgcn_readlane(xh, 63), LO = (uint32_t)__builtin_amdgcn_readlane(xl, 63);
+        if (lane == 0) store_sc1(rowc + g, kGValid | ((uint64_t)HI << 20) | (uint64_t)LO);
+        uint32_t c4[4] = {0, 0, 0, 0};
+        const bool ok = G <= 64 ? poll_counts<1>(rowc, G, g, pa.abort, c4) : poll_counts<4>(rowc, G, g, pa.abort, c4);
+        if (lane == 0) {
+          sh.base_hi = (int)c4[0];
+          sh.base_lo = (int)c4[1];
+          sh.tot_hi = (int)c4[2];
+          sh.tot_lo = (int)c4[3];
+          sh.abort = ok ? 0 : 1;
+          if (!ok) __hip_atomic_fetch_or(pa.abort, i == 0 ? kAbortClean : kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      __syncthreads();
+      if (sh.abort) {
+        done = false;
+        break;
+      }
+      // ranks and the cut (k_cbatch)
+      const int base_hi = sh.base_hi, tot_hi = sh.tot_hi, base_lo = tot_hi + sh.base_lo;
+      total = tot_hi + sh.tot_lo;
+      const uint64_t below = (1ull << lane) - 1;
+      kbits = 0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const int n = lo + j * B + tid;
+        const bool f = (fbits >> j) & 1u, hi = n >= se;
+        const uint64_t bh = __ballot(f && hi), bl = __ballot(f && !hi);
+        const int rank = hi ? base_hi + sh.chi[j * W + wave] + __popcll(bh & below) + 1
+                            : base_lo + sh.clo[j * W + wave] + __popcll(bl & below) + 1;
+        if (f && rank <= KF) kbits |= 1u << j;
+        if (f && rank == KF + 1) sh.pown = hi ? n - se : n + N - se;
+      }
+    }
+    // ---- statistics: the maxima over the feasible (kept) rows; scores only in waves that hold one
+    int mt = 0, mn = 0, nf = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int n = lo + j * B + tid;
+      const bool kept = (kbits >> j) & 1u;
+      if (__ballot(kept) != 0) {
+        NodeEval e{0, 0, 0, 0};
+        if (kept) {
+          if constexpr (kStream) run_scores<SM>(st, q, load_row<kRecip>(st, n), n, e, false);
+          else run_scores<SM>(st, q, r[j], n, e, false);
+          mt = max(mt, e.taint);
+          mn = max(mn, e.na);
+          ++nf;
+        }
+        if constexpr (!kStream) {
+          ep[j] = e.partial;
+          et[j] = e.taint;
+          en[j] = e.na;
+        }
+      }
+    }
+    mt = wave_reduce_max(mt);
+    mn = wave_reduce_max(mn);
+    nf = wave_reduce_sum(nf);
+    if (lane == 0) {
+      nsh.wt[wave] = mt;
+      nsh.wn[wave] = mn;
+      nsh.wf[wave] = nf;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int t = wave_reduce_max(lane < W ? nsh.wt[lane] : 0), a = wave_reduce_max(lane < W ? nsh.wn[lane] : 0);
+      const int f = wave_reduce_sum(lane < W ? nsh.wf[lane] : 0);
+      if (lane == 0)
+        store_sc1(rows + g, kGValid | ((uint64_t)(uint32_t)t << (kNStatFeasBits + kNStatNaBits)) |
+                                ((uint64_t)(uint32_t)a << kNStatFeasBits) | (uint64_t)(uint32_t)f);
+      uint32_t s3[3] = {0, 0, 0};
+      const bool ok = G <= 64 ? poll_stats<1>(rows, G, pa.abort, s3) : poll_stats<4>(rows, G, pa.abort, s3);
+      if (lane == 0) {
+        nsh.feas = (int)s3[0];
+        nsh.maxT = (int)s3[1];
+        nsh.maxNA = (int)s3[2];
+        sh.abort = ok ? 0 : 1;
+        if (!ok) __hip_atomic_fetch_or(pa.abort, i == 0 ? kAbortClean : kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __syncthreads();
+    if (sh.abort) {
+      done = false;
+      break;
+    }
+    // ---- keys over the same rows, with the pod's maxima
+    const int maxT = nsh.maxT, maxNA = nsh.maxNA;
+    if (!cut) total = nsh.feas;
+    const uint64_t tk = pod_tie_key(st.seed, pa.seq0 + i);
+    uint64_t best = 0;
+    int bidx = -1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int loc = j * B + tid, n = lo + loc;
+      const bool kept = (kbits >> j) & 1u;
+      if (__ballot(kept) != 0) {
+        uint64_t key = 0;
+        if (kept) {
+          int64_t tot;
+          if constexpr (kStream) {
+            NodeEval e{0, 0, 0, 0};
+            run_scores<SM>(st, q, load_row<kRecip>(st, n), n, e, false);
+            tot = norm_total(st, e.partial, e.taint, e.na, maxT, maxNA);
+          } else {
+            tot = norm_total(st, ep[j], et[j], en[j], maxT, maxNA);
+          }
+          if (st.n_scores == 0) tot = 1;
+          key = ((uint64_t)(tot + 1) << 40) | rank40(tk, (uint64_t)(st.node_base + n), st.tie_mode);
+        }
+        if (key > best) {
+          best = key;
+          bidx = loc;
+        }
+      }
+    }
+    wave_argmax(best, bidx);
+    if (lane == 0) {
+      sh.wk[wave] = best;
+      sh.wi[wave] = bidx;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      uint64_t k = lane < W ? sh.wk[lane] : 0;
+      int ci = lane < W ? sh.wi[lane] : -1;
+      wave_argmax(k, ci);
+      if (lane == 0) {
+        if (cut && sh.pown >= 0) store_sc1(pa.cpos + i, kGValid | (uint64_t)(uint32_t)sh.pown);
+        store_sc1(rowk + g, kGValid | k);
+      }
+      uint64_t wkey = 0;
+      int wg = -1;
+      bool ok = G <= 64 ? poll_row<1, false>(rowk, G, pa.abort, kGValid, kGValid, wkey, wg)
+                        : poll_row<4, false>(rowk, G, pa.abort, kGValid, kGValid, wkey, wg);
+      int p = N;
+      if (ok && cut && total > KF) {
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+          const uint64_t v = load_sc1(pa.cpos + i);
+          if (v & kGValid) {
+            p = (int)(uint32_t)v;
+            break;
+          }
+          if (load_sc1(pa.abort) != 0 || __builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) {
+            ok = false;
+            break;
+          }
+        }
+      }
+      if (lane == 0) {
+        sh.rkey = wkey;
+        sh.rwg = wg;
+        sh.rp = p;
+        sh.cand = ci;
+        sh.abort = ok ? 0 : 1;
+        if (!ok) __hip_atomic_fetch_or(pa.abort, kAbortDirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __syncthreads();
+    if (sh.abort) {
+      done = false;
+      break;
+    }
+    // ---- the winner assumes and writes the record (a single feasible node is returned unscored; no
+    // feasible node: workgroup 0 writes node = -1); under a cut every workgroup advances the rotation
+    const int wg = sh.rwg, p = sh.rp, cand = sh.cand;
+    if (wg == g && pa.assume && tid == cand % B) {
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        if (j == cand / B) {
+          if constexpr (kStream) {
+            NodeRes t = load_res(st, lo + cand);
+            assume_row(st, q, t, lo + cand);
+          } else {
+            assume_row(st, q, r[j], lo + cand);
+          }
+          assume_counts(st, pa.first + i, lo + cand);
+        }
+    }
+    if (tid == 0 && (wg == g || (wg < 0 && g == 0))) {
+      kgpu_result res;
+      res.node = wg < 0 ? -1 : st.node_base + lo + cand;
+      res.feasible = cut ? min(total, KF) : total;
+      res.evaluated = cut ? p : st.n_total;
+      res.scored = (wg >= 0 && res.feasible >= 2) ? 1 : 0;
+      res.score = res.scored ? (int64_t)(sh.rkey >> 40) - 1 : 0;
+      gp(st.results)[pa.first + i] = res;
+    }
+    if (cut) {
+      s = (s + p) % N;
+      last_p = p;
+    }
+  }
+  if (cut && done && g == 0 && tid == 0) {
+    gp(st.cut_state)[0] = s;
+    gp(st.cut_state)[1] = last_p;
+  }
+}
+
 // ---------------------------------------------------------------- topology pipeline
 // PodTopologySpread (podtopologyspread/{filtering,scoring}.go), InterPodAffinity
 // (interpodaffinity/{filtering,scoring}.go) and DefaultPodTopologySpread
@@ -5010,6 +5347,52 @@ int launch_cbatch(const DevState* st, const BatchArgs& a, int groups, int geo, i
   spec = batch_row(spec);
   if (geo < 0 || geo >= kNumGeo || !a.cgran || !a.cpos) return -1;
   const BatchFn fn = kCutBatch[spec][geo];
+  const int threads = kGeo[geo].B;
+  static bool attr_set[kNumSpecs][kNumGeo] = {};
+  if (!attr_set[spec][geo]) {  // one workgroup per CU, as launch_batch
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kBatchLdsPad) != hipSuccess)
+      return -1;
+    attr_set[spec][geo] = true;
+  }
+  BatchArgs arg = a;
+  const DevState* sp = st;
+  void* args[] = {(void*)&sp, (void*)&arg};
+  if (!coop && grid_fits(reinterpret_cast<const void*>(fn), threads, (size_t)kBatchLdsPad, groups)) {
+    hipLaunchKernelGGL(fn, dim3(groups), dim3(threads), (unsigned)kBatchLdsPad, (hipStream_t)stream, sp, arg);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  arg.hold = -1;  // every workgroup of a cooperative launch is resident
+  return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(fn), dim3(groups), dim3(threads), args,
+                                    (unsigned)kBatchLdsPad, (hipStream_t)stream) == hipSuccess
+             ? 0
+             : -1;
+}
+
+// normalize-pass runs: [profile spec][geometry], the geometry table of k_batch.  The Fit row scores with no
+// normalized plugin and can never need the pass: no instantiation, and the launcher refuses it.
+template <uint32_t FM, uint32_t SM>
+struct NormRow {
+  static constexpr BatchFn fn[kNumGeo] = {k_nbatch<FM, SM, 1, 64>,  k_nbatch<FM, SM, 1, 128>, k_nbatch<FM, SM, 1, 192>,
+                                          k_nbatch<FM, SM, 1, 448>, k_nbatch<FM, SM, 1, 960>, k_nbatch<FM, SM, 4, 512>,
+                                          k_nbatch<FM, SM, 8, 512>};
+};
+static const BatchFn* const kNormBatch[] = {
+    NormRow<kRuntime, kRuntime>::fn,
+    nullptr,
+    NormRow<kDefaultFM, kDefaultSM>::fn,
+    NormRow<kDefaultFM, kAutoscalerSM>::fn,
+};
+static_assert(sizeof(kNormBatch) / sizeof(kNormBatch[0]) == kNumSpecs, "one k_nbatch row per profile instantiation");
+static_assert(((kFitSM >> KGPU_S_TAINT_TOLERATION) & 1u) == 0 && ((kFitSM >> KGPU_S_NODE_AFFINITY) & 1u) == 0,
+              "the Fit row has no normalized plugin");
+
+bool nbatch_row_ok(int spec) { return kNormBatch[batch_row(spec)] != nullptr; }
+
+int launch_nbatch(const DevState* st, const BatchArgs& a, int groups, int geo, int spec, bool coop, void* stream) {
+  spec = batch_row(spec);
+  if (geo < 0 || geo >= kNumGeo || !a.cgran || kNormBatch[spec] == nullptr) return -1;
+  const BatchFn fn = kNormBatch[spec][geo];
   const int threads = kGeo[geo].B;
   static bool attr_set[kNumSpecs][kNumGeo] = {};
   if (!attr_set[spec][geo]) {  // one workgroup per CU, as launch_batch
