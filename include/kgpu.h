@@ -720,6 +720,14 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * refuse these pods.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured inside the launch as in
  * k_cbatch; nextStartNodeIndex stays continuous with every other path. */
 #define KGPU_OPT_NORM_PERSISTENT 26
+/* KGPU_OPT_BATCH_EARLY_PUBLISH (27): 1 (default) = the helper-wave instantiation of the persistent batch
+ * kernel (KGPU_OPT_BATCH_HELPER) publishes both variants of a pod -- the rows as they are, and with the
+ * previous pod assumed on this workgroup's candidate -- as soon as they are evaluated, and every reader picks
+ * the variant once it knows the previous winner; the granule and feasible-count areas of such a run double.
+ * 0 = one granule per pod and workgroup, published after the previous pod resolved.  Same results either
+ * way; read at launch.  The environment variable KGPU_BATCH_EARLY_PUBLISH=0|1 sets a new engine's initial
+ * value (measurement of unmodified callers). */
+#define KGPU_OPT_BATCH_EARLY_PUBLISH 27
 int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
 /* Engine counters: out[0] = calls issued again with a cooperative launch after a persistent run's
  * workgroups were not all resident before its first pod (KGPU_OPT_COOPERATIVE); out[1] = persistent

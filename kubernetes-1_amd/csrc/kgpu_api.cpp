@@ -228,6 +228,7 @@ struct kgpu_ctx {
   std::vector<std::array<int64_t, kHt>> ht_batches; // the same for longer calls (kgpu_schedule_batch)
   bool tc_on = true;                               // KGPU_OPT_TOPO_RESIDENT
   bool batch_helper = true;                        // KGPU_OPT_BATCH_HELPER
+  bool batch_early = true;                         // KGPU_OPT_BATCH_EARLY_PUBLISH
   bool topo_ahead = true;                          // KGPU_OPT_TOPO_AHEAD
   int tbatch_geo_first = 1;                        // KGPU_OPT_TBATCH_GEO (256 x 1 measured equal: 512 x 1 stays)
   size_t ar_limit = 1 << 20;                       // KGPU_OPT_ARENA_BYTES (bytes of arena items per cycle)
@@ -2526,8 +2527,10 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
         ba.xseq0 = c->xg_seq;
         c->xg_seq += cnt;
       } else {
-        // layout: granules [cnt][groups] u64 | feasible counts [cnt][groups] i32
-        const size_t cells = (size_t)cnt * (size_t)groups;
+        // layout: granules [cnt][groups] u64 | feasible counts [cnt][groups] i32; under early publish a slot
+        // holds both variants: two of each
+        ba.dual = c->batch_early && kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper) ? 1 : 0;
+        const size_t cells = (size_t)cnt * (size_t)groups * (ba.dual ? 2 : 1);
         const size_t gbytes = sizeof(uint64_t) * cells + sizeof(int32_t) * cells;
         if ((rc = ensure(c, c->gran, gbytes))) return rc;
         HIP_OK(c, hipMemsetAsync(c->gran.p, 0, sizeof(uint64_t) * cells, c->stream));
@@ -3483,7 +3486,10 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
     HIP_OK(c, hipHostMalloc(&ps.host, bytes * 2, hipHostMallocDefault));
     ps.host_cap = bytes * 2;
   }
-  const size_t cells = (size_t)n * (size_t)groups;
+  // (early publish: a slot holds both variants, so both areas double -- and with them what the other
+  // slot's fixup zeroes)
+  const bool dual = c->batch_early && kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper);
+  const size_t cells = (size_t)n * (size_t)groups * (dual ? 2 : 1);
   const size_t gbytes = (sizeof(uint64_t) + sizeof(int32_t)) * cells;
   if (ps.gran.bytes < gbytes) {
     if ((rc = ensure(c, ps.gran, gbytes))) return rc;
@@ -3531,6 +3537,7 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   ba.rank = 0;
   ba.GT = groups;
   ba.R = 0;
+  ba.dual = dual ? 1 : 0;
   ba.first = 0;
   ba.count = n;
   ba.per = per;
@@ -3765,6 +3772,7 @@ int kgpu_create(const kgpu_config* cfg, kgpu_ctx** out) try {
     if (e && e[0] == '1') (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
   }
   if (const char* e = std::getenv("KGPU_HOST_TRACE")) c->htrace = e[0] == '1';
+  if (const char* e = std::getenv("KGPU_BATCH_EARLY_PUBLISH")) c->batch_early = e[0] != '0';
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
     return KGPU_E_DEVICE;
   hipDeviceProp_t prop;
@@ -3996,6 +4004,7 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_COOPERATIVE) c->coop = value != 0;
   else if (option == KGPU_OPT_BATCH_GEO) c->batch_geo_first = (int)std::min<int64_t>(std::max<int64_t>(0, value), 6);
   else if (option == KGPU_OPT_BATCH_HELPER) c->batch_helper = value != 0;
+  else if (option == KGPU_OPT_BATCH_EARLY_PUBLISH) c->batch_early = value != 0;
   else if (option == KGPU_OPT_TOPO_AHEAD) c->topo_ahead = value != 0;
   else if (option == KGPU_OPT_TBATCH_GEO) c->tbatch_geo_first = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4);
   else if (option == KGPU_OPT_TOPO_RESIDENT) {

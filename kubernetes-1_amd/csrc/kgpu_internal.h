@@ -274,7 +274,9 @@ struct BatchArgs {
                             // wait times out (-1: never)
   int32_t hold;         // KGPU_OPT_HOLD_GROUP test hook: this workgroup leaves at once (an ordinary launch
                         // whose workgroup never became resident; -1: none)
-  int32_t pad_h;
+  int32_t dual;         // KGPU_OPT_BATCH_EARLY_PUBLISH on the helper-wave instantiation: a slot is two granules
+                        // {variant A, variant B} (16-byte aligned) and two feasible counts, so gran is
+                        // [count][groups][2] and feas [count][groups][2]; 0: one of each
   // pipelined batches (kgpu_schedule_batch_submit): k_batch_fixup also writes every record into pinned host
   // memory (res_out), copies the run's abort word there (abort_out), and zeroes the other pipeline slot's
   // granule area for the batch after next (zero_buf, zero_n16 16-byte words); all null / 0 otherwise

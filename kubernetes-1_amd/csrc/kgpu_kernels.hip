@@ -1581,6 +1581,69 @@ __device__ __forceinline__ bool poll_row(const uint64_t* row, int G, const int32
   }
 }
 
+// Early publish (the helper-wave instantiation, EP): a pod's slot is two granules, variant A and variant B,
+// each with its own valid bit, published by the row wave before the previous pod resolves.  The reader takes
+// B from the slot of the workgroup that won the pod before (`wb`, -1: none) and A from every other; a slot
+// counts only once BOTH words carry the tag, so nothing rests on the 16-byte store arriving whole.
+template <int NJ>
+struct Sweep2 {
+  uint64_t a[NJ], b[NJ];
+  int abort;
+};
+template <int NJ>
+__device__ __forceinline__ Sweep2<NJ> sweep2(const uint64_t* row, int G, const int32_t* abort_word, uint64_t fill) {
+  const int lane = threadIdx.x & 63;
+  Sweep2<NJ> s;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const uint64_t* p = row + 2 * (lane + 64 * j);
+    const bool in = lane + 64 * j < G;
+    s.a[j] = in ? load_sc1(p) : fill;  // a valid granule with key 0
+    s.b[j] = in ? load_sc1(p + 1) : fill;
+  }
+  s.abort = load_sc1(abort_word);
+  return s;
+}
+template <int NJ>
+__device__ __forceinline__ bool row_done2(const Sweep2<NJ>& cur, int wb, uint64_t& wkey, int& wg) {
+  const int lane = threadIdx.x & 63;
+  bool all = true;
+  uint64_t k = 0;
+  int gsel = -1;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (!(cur.a[j] & cur.b[j] & kGValid)) {
+      all = false;
+    } else {
+      const uint64_t v = (lane + 64 * j == wb ? cur.b[j] : cur.a[j]) & ~kGValid;
+      if (v > k) {
+        k = v;
+        gsel = lane + 64 * j;
+      }
+    }
+  }
+  if (!__all(all)) return false;
+  wave_argmax(k, gsel);
+  wkey = k;
+  wg = k ? gsel : -1;
+  return true;
+}
+template <int NJ>
+__device__ __forceinline__ bool poll_row2(const uint64_t* row, int G, const int32_t* abort_word, int wb, uint64_t& wkey,
+                                          int& wg) {
+  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+  Sweep2<NJ> a = sweep2<NJ>(row, G, abort_word, kGValid);
+  for (;;) {
+    const Sweep2<NJ> b = sweep2<NJ>(row, G, abort_word, kGValid);
+    if (a.abort != 0) return false;
+    if (row_done2<NJ>(a, wb, wkey, wg)) return true;
+    a = sweep2<NJ>(row, G, abort_word, kGValid);
+    if (b.abort != 0) return false;
+    if (row_done2<NJ>(b, wb, wkey, wg)) return true;
+    if (__builtin_amdgcn_s_memrealtime() - t0 > kSpinTimeout) return false;
+  }
+}
+
 // HB (config (b)'s profile, one row wave): two helper waves beside the row wave evaluate the rows'
 // NodeResourcesLeastAllocated (helper 1) and BalancedAllocation (helper 2) weighted scores of each pod
 // while the row wave evaluates NodeResourcesFit and the tie-break ranks -- three instruction streams on
@@ -1637,12 +1700,18 @@ __device__ __forceinline__ kgpu_pod_query ring_uniform(kgpu_pod_query q) {
 // XG: the node-sharded instantiation (xGMI mailbox rings); the unsharded one carries none of its code.
 // TR (helper-wave instantiation only): the phase stamps are compiled in; without it that instantiation
 // carries none.  The others test BatchArgs.trace at run time.
-template <uint32_t FM, uint32_t SM, int K, int B, bool XG, bool HB = false, bool TR = false>
+// EP (helper-wave instantiation only; KGPU_OPT_BATCH_EARLY_PUBLISH): the row wave publishes both variants of
+// pod i as soon as its partials exist and the readers select (Sweep2 above), so the communication wave only
+// resolves: barrier (c), the combine and the store issue leave the store -> hop -> resolve chain.  A
+// workgroup that may win pod i-1 and holds no variant B (pod i-1 changes memory-resident columns, or its
+// own row went through the slow path) defers its store to after barrier (c) and publishes {K, K}.
+template <uint32_t FM, uint32_t SM, int K, int B, bool XG, bool HB = false, bool TR = false, bool EP = false>
 __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevState* __restrict__ stp, BatchArgs pa) {
   static_assert(!HB || (B == 64 && !XG &&
                        SM == ((1u << KGPU_S_BALANCED_ALLOCATION) | (1u << KGPU_S_LEAST_ALLOCATED) | kDefRes)),
                 "the helper wave splits config (b)'s profile on the one-row-wave geometry");
   static_assert(HB || !TR, "only the helper-wave instantiation has a traced twin");
+  static_assert(HB || !EP, "only the helper-wave instantiation publishes early");
   const DevState& st = *stp;
   constexpr int W = B / 64;  // row waves; wave W communicates; HB: waves W + 1, W + 2 help row wave 0
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1695,9 +1764,23 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       }
     }
   };
+  // EP: both variants of pod i (and their feasible counts) into this workgroup's 16-byte slot, by one lane:
+  // one write-through 16-byte vector store.  (An asm statement: the atomic builtins stop at 8 bytes.  The
+  // compiler counts no vmcnt event for it, so it puts no wait into the row loop; the trailing s_nop keeps the
+  // next instruction off the data registers until the store has read them.)
+  auto publish2 = [&](int i, uint64_t ka, uint64_t kb, int fa, int fb) {
+    const size_t roff = (size_t)i * GT + gme;
+    typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
+    const uint64_t wa = kGValid | ka, wb = kGValid | kb;
+    const u32x4 v = {(uint32_t)wa, (uint32_t)(wa >> 32), (uint32_t)wb, (uint32_t)(wb >> 32)};
+    GAS uint64_t* gp2 = (GAS uint64_t*)(pa.gran + 2 * roff);
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(gp2), "v"(v) : "memory");
+    reinterpret_cast<int2*>(pa.feas)[roff] = int2{fa, fb};
+  };
   // phase stamps (diagnostics): per iteration i, 8 per traced workgroup (0 and last).  Row wave 0:
   // 0 start, 5 evaluated, 1 partials written, 2 past barrier (c), 4 iteration end.  The
-  // communication wave: 7 pod i-1 resolved, 6 pod i's partials complete, 3 pod i published.
+  // communication wave: 7 pod i-1 resolved, 6 pod i's partials complete, 3 pod i published (EP: stamps 6
+  // and 3 come from the row wave, around its early store).
   const bool tr = pa.trace && (g == 0 || g == G - 1);
   int64_t* trow = pa.trace ? pa.trace + (g == 0 ? 0 : 8) : nullptr;
   constexpr bool kStamps = !HB || TR;
@@ -1806,6 +1889,7 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
     //      pod i-1's result record
     int cand = -1;        // this workgroup's candidate for pod i-1 (what it published)
     bool staged = false;  // its row is staged for variant B
+    int wprev = -1;       // EP: the workgroup that won pod i-2, whose slot of pod i-1 is read as variant B
     for (int i = 0; i <= pa.count; ++i) {
       const bool have_prev = i > 0, have_cur = i < pa.count;
       const int p = i & 1;
@@ -1836,7 +1920,10 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       if (have_prev) {
         const uint64_t* prow = pa.gran + ring_row(i - 1) * GT;
         const uint64_t expect = ring_tag(i - 1);
-        if constexpr (!XG)
+        if constexpr (EP)
+          ok = GT <= 128 ? poll_row2<2>(pa.gran + (size_t)(i - 1) * 2 * GT, GT, pa.abort, wprev, wkey, wg)
+                         : poll_row2<4>(pa.gran + (size_t)(i - 1) * 2 * GT, GT, pa.abort, wprev, wkey, wg);
+        else if constexpr (!XG)
           ok = poll_row<4, false>(prow, GT, pa.abort, tmask, expect, wkey, wg);
         else if (GT <= 256)
           ok = poll_row<4, true>(prow, GT, pa.abort, tmask, expect, wkey, wg);
@@ -1844,6 +1931,7 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
           ok = poll_row<16, true>(prow, GT, pa.abort, tmask, expect, wkey, wg);
         KGPU_STAMP(i, 7);
       }
+      wprev = wg;
       const bool won = have_prev && wg == gme;
       const bool slow = have_cur && won && pa.assume && !fast_b;
       if (ok) {
@@ -1876,10 +1964,12 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       if (!ok) break;
       int cn = -1;
       if (have_cur && !slow) {
-        KGPU_STAMP(i, 6);
+        if constexpr (!EP) KGPU_STAMP(i, 6);
         const Cand c = wg_combine<B>(sh, p, won && fast_b);
-        if (lane == 0) publish(i, c.key, c.feas);
-        KGPU_STAMP(i, 3);
+        if constexpr (!EP) {
+          if (lane == 0) publish(i, c.key, c.feas);
+          KGPU_STAMP(i, 3);
+        }
         cn = c.key ? c.idx : -1;
       }
       if constexpr (HB) {
@@ -1942,6 +2032,7 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
     const int ob = cand >= 0 ? cand % B : -1, jb = cand >= 0 ? cand / B : -1;
     uint64_t keys[K];
     Cand own_a{0, -1, 0}, own_b{0, -1, 0};  // this wave's variant-A / B reduction of pod i
+    bool defer = false;                     // EP: pod i's store waits for barrier (c)
     if (have_cur) {
       const uint64_t tk = pod_tie_key(st.seed, pa.seq0 + i);
       if (fast_b && wave == W - 1) {
@@ -1995,6 +2086,17 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       }
       KGPU_STAMP(i, 5);
       wg_partials<K, B>(sh, p, keys, fast_b, ob, jb, cand, own_a, own_b);
+      if constexpr (EP) {
+        // both variants out before pod i-1 resolves (B = A where this workgroup cannot win pod i-1 or its
+        // win changes nothing); deferred where it may win and holds no variant B
+        defer = have_prev && cand >= 0 && pa.assume && !fast_b;
+        KGPU_STAMP(i, 6);
+        if (!defer) {
+          if (lane == 0)
+            publish2(i, own_a.key, fast_b ? own_b.key : own_a.key, own_a.feas, fast_b ? own_b.feas : own_a.feas);
+          KGPU_STAMP(i, 3);
+        }
+      }
     }
     KGPU_STAMP(i, 1);
     // the next pod's query (HB: it came out of the query ring at the top of the iteration, kQRing):
@@ -2061,7 +2163,8 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
         }
         const Cand c = wave_recombine<K, B>(sh, p, keys);
         if (lane == 0) {
-          publish(i, c.key, c.feas);
+          if constexpr (EP) publish2(i, c.key, c.key, c.feas, c.feas);
+          else publish(i, c.key, c.feas);
           sh.cslow[p] = c.key ? c.idx : -1;
           lds_release(&sh.cready, i + 1);
         }
@@ -2069,6 +2172,13 @@ __global__ __launch_bounds__(B + 64 + (HB ? 2 * B : 0)) void k_batch(const DevSt
       lds_wait(&sh.cready, i + 1, pa.abort);
       cand = sh.cslow[p];
     } else {
+      if constexpr (EP) {
+        // deferred and not won: variant A is pod i's key here whoever won pod i-1
+        if (have_cur && defer) {
+          if (lane == 0) publish2(i, own_a.key, own_a.key, own_a.feas, own_a.feas);
+          KGPU_STAMP(i, 3);
+        }
+      }
       cand = cn;
       if (W > 1 && cand >= 0 && tid == cand % B) {
         // stage pod i's candidate row (pod i-1 already assumed on it) for pod i+1's variant B
@@ -2108,7 +2218,18 @@ __global__ __launch_bounds__(256) void k_batch_fixup(const DevState* __restrict_
   if (i >= pa.count) return;
   const size_t row = pa.R > 0 ? (size_t)((pa.xseq0 + i) % pa.R) : (size_t)i;
   int f = 0;
-  for (int g = lane; g < pa.GT; g += 64) f += pa.feas[row * pa.GT + g];
+  if (pa.dual) {
+    // early publish: two counts per slot; variant B's where the workgroup won the pod before (its index
+    // from that pod's record: a workgroup's nodes are [g * per, (g + 1) * per)), variant A's elsewhere
+    int wb = -1;
+    if (i > 0) {
+      const int pn = gp(st.results)[pa.first + i - 1].node;
+      if (pn >= 0) wb = (pn - st.node_base) / pa.per;
+    }
+    for (int g = lane; g < pa.GT; g += 64) f += pa.feas[(row * pa.GT + g) * 2 + (g == wb ? 1 : 0)];
+  } else {
+    for (int g = lane; g < pa.GT; g += 64) f += pa.feas[row * pa.GT + g];
+  }
   f = (int)wave_sum32((uint32_t)f);
   (void)G;
   if (lane == 0) {
@@ -5221,13 +5342,16 @@ using BatchFn = void (*)(const DevState*, BatchArgs);
 // the helper-wave instantiation (HB) of config (b)'s profile on the one-row-wave geometry
 template <uint32_t FM, uint32_t SM, bool E>
 struct HelperFn {
-  static constexpr BatchFn fn = nullptr, traced = nullptr;
+  static constexpr BatchFn fn = nullptr, traced = nullptr, early = nullptr, early_traced = nullptr;
 };
 template <uint32_t FM, uint32_t SM>
 struct HelperFn<FM, SM, true> {
   static constexpr BatchFn fn = k_batch<FM, SM, 1, 64, false, true>;
   // its twin with the phase stamps compiled in (BatchArgs.trace set: KGPU_OPT_PHASE_TRACE)
   static constexpr BatchFn traced = k_batch<FM, SM, 1, 64, false, true, true>;
+  // both with early publish (KGPU_OPT_BATCH_EARLY_PUBLISH, BatchArgs.dual)
+  static constexpr BatchFn early = k_batch<FM, SM, 1, 64, false, true, false, true>;
+  static constexpr BatchFn early_traced = k_batch<FM, SM, 1, 64, false, true, true, true>;
 };
 static const BatchFn kBatchHelper[] = {
     nullptr,
@@ -5238,6 +5362,18 @@ static const BatchFn kBatchHelper[] = {
 static const BatchFn kBatchHelperTraced[] = {
     nullptr,
     HelperFn<kFitFM, kFitSM, true>::traced,
+    nullptr,
+    nullptr,
+};
+static const BatchFn kBatchHelperEarly[] = {
+    nullptr,
+    HelperFn<kFitFM, kFitSM, true>::early,
+    nullptr,
+    nullptr,
+};
+static const BatchFn kBatchHelperEarlyTraced[] = {
+    nullptr,
+    HelperFn<kFitFM, kFitSM, true>::early_traced,
     nullptr,
     nullptr,
 };
@@ -5297,10 +5433,14 @@ int launch_batch(const DevState* st, const BatchArgs& a, int groups, int geo, in
   const int x = a.R > 0 ? 1 : 0;  // node-sharded over xGMI mailboxes
   const bool hb = batch_helper_used(spec, geo, x != 0, helper);
   const bool traced = hb && a.trace != nullptr;
-  const BatchFn fn = hb ? (traced ? kBatchHelperTraced : kBatchHelper)[spec] : (x ? kBatchX : kBatch)[spec][geo];
+  const bool early = a.dual != 0;  // the caller sized the granule area for it (batch_helper_used)
+  if (early && !hb) return -1;
+  const BatchFn fn = hb ? (early ? (traced ? kBatchHelperEarlyTraced : kBatchHelperEarly)
+                                 : (traced ? kBatchHelperTraced : kBatchHelper))[spec]
+                        : (x ? kBatchX : kBatch)[spec][geo];
   const int threads = kGeo[geo].B + 64 + (hb ? 2 * kGeo[geo].B : 0);
-  static bool attr_set[4][kNumSpecs][kNumGeo] = {};
-  const int ai = hb ? (traced ? 3 : 2) : x;
+  static bool attr_set[6][kNumSpecs][kNumGeo] = {};
+  const int ai = hb ? (traced ? 3 : 2) + (early ? 2 : 0) : x;
   if (!attr_set[ai][spec][geo]) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kBatchLdsPad) != hipSuccess)

@@ -7,7 +7,10 @@ row wave and the communication wave; post = pod i-1 assumed, pod i's candidate r
 loop overhead.  Communication wave: poll_vs_rows = pod i-1 resolved minus wave 0's partials of
 pod i (positive: the granule hop, not the evaluation, sets the pace); publish = pod i published
 after the later of its partials and pod i-1's resolution; hop = latest publish of pod i (of the
-two traced workgroups) to pod i seen resolved."""
+two traced workgroups) to pod i seen resolved.  Under KGPU_OPT_BATCH_EARLY_PUBLISH (--early-publish 0 / 1; default:
+the library's) the row wave publishes, right after its partials: `publish` is then that store against the
+later of barrier (c) and pod i-1's resolution -- negative by about the time the store left the chain --
+and the hop runs from the row wave's store."""
 
 import argparse
 import os
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--config", default="b")
     ap.add_argument("--groups", type=int, default=0, help="KGPU_OPT_PERSIST_GROUPS cap (0: one per CU)")
     ap.add_argument("--batch-geo", type=int, default=None, help="KGPU_OPT_BATCH_GEO")
+    ap.add_argument("--early-publish", type=int, default=None, help="KGPU_OPT_BATCH_EARLY_PUBLISH")
     args = ap.parse_args()
     import numpy as np
     from kgpu import abi, cluster
@@ -41,6 +45,8 @@ def main():
     eng.set_option(abi.OPT_PHASE_TRACE, 1)
     if args.batch_geo is not None:
         eng.set_option(abi.OPT_BATCH_GEO, args.batch_geo)
+    if args.early_publish is not None:
+        eng.set_option(abi.OPT_BATCH_EARLY_PUBLISH, args.early_publish)
     if args.groups:
         eng.set_option(abi.OPT_PERSIST_GROUPS, args.groups)
     eng.schedule_batch(q, pc)
