@@ -207,3 +207,59 @@ def topo_cluster(seed, n_nodes=16, n_existing=24, n_pods=30):
     rss = [{"metadata": {"name": "rs-db", "namespace": "default"},
             "spec": {"selector": {"matchLabels": {"app": "db"}}}}]
     return nodes, existing, pods, services, rss
+
+
+# ---------------------------------------------------------------- routing families (test_random_routing.py)
+# name -> (nodes, cut percentage, numFeasibleNodesToFind at that percentage): the smallest sizes at which
+# every persistent kernel has at least two workgroups (63 nodes per k_batch workgroup at 64 x 1, 256 per
+# k_tbatch workgroup) and the percentage cuts (N >= 100, to_find < N)
+FAMILIES = {"generic_taints": (200, 50, 100), "generic_plain": (330, 31, 102), "topo": (400, 25, 100)}
+FAMILY_PODS = 48
+
+
+def family(name, seed):
+    """(nodes, existing, pods, services, rss) of one routing family.  generic_taints: cluster() as it is
+    (spot / noisy PreferNoSchedule taints make nearly every pod a normalize-pass pod); generic_plain: no
+    PreferNoSchedule taint on any node, so only a preferred node-affinity term makes one; topo:
+    topo_cluster() with 24 existing pods (with N / 2 of them few pods keep enough feasible nodes to be cut)."""
+    n = FAMILIES[name][0]
+    if name == "topo":
+        return topo_cluster(seed, n, 24, FAMILY_PODS)
+    nodes, existing, pods = cluster(seed, n, n // 2, FAMILY_PODS)
+    if name == "generic_plain":
+        for nd in nodes:
+            taints = [t for t in nd["spec"].get("taints", []) if t["effect"] != "PreferNoSchedule"]
+            if taints:
+                nd["spec"]["taints"] = taints
+            else:
+                nd["spec"].pop("taints", None)
+    return nodes, existing, pods, [], []
+
+
+def family_calls(seed, n_pods=FAMILY_PODS):
+    """The call sequence a family's pods are scheduled in, from the seed alone: four to six batches
+    ("batch", lo, hi) of random length, a one-pod and a two-pod batch among them, and two one-pod
+    diagnostic cycles ("one", k), each between two batches."""
+    r = random.Random(7000 + seed)
+    nb = r.choice([4, 5, 6])
+    rest = n_pods - 2 - 3  # two ("one", k) cycles, the one-pod and the two-pod batch
+    lens, prev = [], 0
+    for c in sorted(r.sample(range(3, rest - 2), nb - 3)) + [rest]:
+        lens.append(c - prev)
+        prev = c
+    # batches of at least three pods: move pods from the longest to any shorter one
+    while min(lens) < 3:
+        lens[lens.index(max(lens))] -= 1
+        lens[lens.index(min(lens))] += 1
+    lens += [1, 2]
+    r.shuffle(lens)
+    ones = set(r.sample(range(1, nb), 2))  # the gaps (before batch g) that hold a diagnostic cycle
+    calls, k = [], 0
+    for g, ln in enumerate(lens):
+        if g in ones:
+            calls.append(("one", k))
+            k += 1
+        calls.append(("batch", k, k + ln))
+        k += ln
+    assert k == n_pods
+    return calls

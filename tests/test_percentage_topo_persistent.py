@@ -43,12 +43,12 @@ SEL = {"matchLabels": {"app": "web"}}
 
 
 class _TCase(_Case):
-    """_Case with the objects DefaultSelector lists (services)."""
+    """_Case with the objects DefaultSelector lists (services, replica sets)."""
 
-    def __init__(self, prof, nodes, existing, pods, calls=None, services=()):
+    def __init__(self, prof, nodes, existing, pods, calls=None, services=(), rss=()):
         from oracle.cref import RefEngine
-        self.fw = GpuFramework(prof, nodes, existing, cluster=Cluster(services=list(services), rss=[]), pods_hint=pods,
-                               create_engine=False)
+        self.fw = GpuFramework(prof, nodes, existing, cluster=Cluster(services=list(services), rss=list(rss)),
+                               pods_hint=pods, create_engine=False)
         self.q, self.pc, _, errs = self.fw.compile_pods(pods)
         assert not errs
         self.n = self.fw.snap.n_nodes

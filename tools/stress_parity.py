@@ -6,6 +6,7 @@ reference (oracle/c), and the assumed node rows after the run.  Prints one line 
 summary; exits non-zero on the first mismatch.  Checker only: the product path is what is measured.
 
   python tools/stress_parity.py --seeds 60 --start 1000      (GPU box)
+  python tools/stress_parity.py --family topo --family generic_plain --norm-persistent 1 --seeds 300
 """
 import argparse
 import json
@@ -97,6 +98,68 @@ def run_family(tag, make, seeds, one_pod_every, variant="default"):
     return line
 
 
+def run_routing_family(name, seeds, pct, norm_persistent, variant="default"):
+    """One of gen_random.FAMILIES (the sizes at which every persistent kernel has two workgroups and
+    percentageOfNodesToScore cuts) through today's routing of kgpu_schedule_batch: the seed's call sequence
+    (gen_random.family_calls: batches of random length with kgpu_schedule_one cycles between them) on one
+    engine and one nextStartNodeIndex rotation, KGPU_OPT_NORM_PERSISTENT as given; the reference schedules
+    the same spans.  `evaluated` is compared too."""
+    import gen_random
+    from kgpu import abi
+    from kgpu.compile import Cluster
+    from kgpu.framework import GpuFramework
+    from oracle.cref import RefEngine
+    tag = "%s pct %d norm %d" % (name, pct, norm_persistent)
+    fields = FIELDS + ("evaluated",)
+    pods_total, t0 = 0, time.time()
+    kinds = {"cut_persistent_pods": 0, "cut_topo_persistent_pods": 0, "norm_persistent_pods": 0}
+    for s in seeds:
+        nodes, ex, pods, services, rss = gen_random.family(name, s)
+        calls = gen_random.family_calls(s, len(pods))
+        prof = make_profile(variant)
+        prof.percentage_of_nodes_to_score = pct
+        fw = GpuFramework(prof, nodes, ex, cluster=Cluster(services=services, rss=rss), pods_hint=pods)
+        q, pc, _, errs = fw.compile_pods(pods)
+        if errs:  # a seed that does not compile is no input
+            print("  %s seed %d: skipped (%d compile errors)" % (tag, s, len(errs)), flush=True)
+            fw.engine.close()
+            continue
+        spans = [(c[1], c[2]) if c[0] == "batch" else (c[1], c[1] + 1) for c in calls]
+        ref = RefEngine(fw.config, fw.snap, threads=8)
+        want = np.concatenate([ref.schedule(q[a:b], pc, first_seq=a) for a, b in spans])
+        fw.engine.set_option(abi.OPT_NORM_PERSISTENT, norm_persistent)
+        got = {f: [] for f in fields}
+        for c in calls:
+            if c[0] == "batch":
+                res, _ = fw.engine.schedule_batch(q[c[1]:c[2]], pc, first_seq=c[1])
+                for f in fields:
+                    got[f].extend(int(x) for x in res[f])
+            else:
+                r, _ = fw.engine.schedule_one(q[c[1]], pc, seq=c[1], assume=True)
+                for f in fields:
+                    got[f].append(int(r[f]))
+        for f in fields:
+            bad = np.nonzero(np.asarray(want[f]) != np.asarray(got[f]))[0]
+            if len(bad):
+                raise AssertionError("%s seed %d calls %s: %s differs at pods %s (want %s, got %s)" %
+                                     (tag, s, calls, f, bad[:5].tolist(), np.asarray(want[f])[bad[:5]].tolist(),
+                                      np.asarray(got[f])[bad[:5]].tolist()))
+        _compare(tag, s, want, got, ref.read_nodes(), fw.engine.read_nodes(fw.snap.n_nodes))
+        cnt = fw.engine.counters()
+        for k in kinds:
+            kinds[k] += cnt[k]
+        fw.engine.close()
+        ref.close()
+        pods_total += len(pods)
+        if s % 20 == 0:
+            print("  %s seed %d: ok" % (tag, s), flush=True)  # progress (the box's silence limit)
+    line = {"family": name, "variant": variant, "pct": pct, "norm_persistent": norm_persistent, "clusters": len(seeds),
+            "pods": pods_total, "seconds": round(time.time() - t0, 1)}
+    line.update(kinds)
+    print(json.dumps(line), flush=True)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", type=int, default=40)
@@ -106,9 +169,20 @@ def main():
                     help="the profile setting the sweep changes (make_profile)")
     ap.add_argument("--long-runs", action="store_true", help="two families of long topology runs instead")
     ap.add_argument("--long-generic", action="store_true", help="two families of long generic batches instead")
+    ap.add_argument("--family", action="append", choices=["generic_taints", "generic_plain", "topo"],
+                    help="a routing family of tests/gen_random.py instead (repeatable): the seed's call sequence "
+                         "through kgpu_schedule_batch's routing under a cut")
+    ap.add_argument("--pct", type=int, default=None, help="with --family: percentageOfNodesToScore (default: the "
+                                                          "family's cut percentage)")
+    ap.add_argument("--norm-persistent", type=int, default=0, metavar="V", help="with --family: KGPU_OPT_NORM_PERSISTENT")
     a = ap.parse_args()
     import gen_random
     seeds = list(range(a.start, a.start + a.seeds))
+    if a.family:
+        out = [run_routing_family(f, seeds, gen_random.FAMILIES[f][1] if a.pct is None else a.pct, a.norm_persistent,
+                                  a.variant) for f in a.family]
+        print(json.dumps({"stress_parity": "ok", "families": out}))
+        return
     fams = [
         ("generic 20 nodes", lambda s: gen_random.cluster(s, n_nodes=20, n_existing=15, n_pods=30)),
         ("generic 700 nodes", lambda s: gen_random.cluster(s, n_nodes=700, n_existing=400, n_pods=60)),
