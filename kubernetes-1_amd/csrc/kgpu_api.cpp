@@ -152,6 +152,7 @@ struct kgpu_ctx {
   std::vector<int32_t> row_canon;                  // [N] first row of the row's node (local index)
   std::unordered_map<int32_t, std::vector<int32_t>> alias_rows;  // canonical row -> all its rows
   bool has_alias = false;
+  bool in_alias = false;  // inside run_batch_once's one-pod-at-a-time loop over an aliased list
   // ---- nominator (kgpu_set_nominated): owned copies of the records and of their pools
   struct Nominator {
     std::vector<kgpu_nominated> list;
@@ -327,6 +328,7 @@ struct kgpu_ctx {
   DevBuf shard;   // send key | send stat | keys [2][kMaxRanks] | stats [2][kMaxRanks]
   DevBuf cut_buf;  // DevState::cut_state (nextStartNodeIndex, last EvaluatedNodes)
   bool cut_init = false;
+  bool cut_fold = false;  // the list has no cut and cut_buf may hold an index of a longer one (fold_rotation)
 };
 
 namespace {
@@ -2091,6 +2093,59 @@ int stage_h2d(kgpu_ctx* c, void* dst, const void* src, size_t bytes) {
   return KGPU_OK;
 }
 
+// A cycle without a cut still stores nextStartNodeIndex = (nextStartNodeIndex + processedNodes) % len(allNodes)
+// with processedNodes = N (generic_scheduler.go:487): an index kept from a longer list is folded into this
+// one, and a later list under a cut starts from the folded value.  No kernel reads cut_buf while cut_state
+// is null, so the first such cycle after a node-list rebuild folds it here, once.
+int fold_rotation(kgpu_ctx* c) {
+  c->cut_fold = false;
+  const int32_t N = c->st.n_total;
+  if (N <= 0 || !c->cut_buf.p) return KGPU_OK;
+  int32_t s = 0;
+  HIP_OK(c, hipMemcpy(&s, c->cut_buf.p, sizeof(s), hipMemcpyDeviceToHost));
+  if (s >= N) {
+    s %= N;
+    HIP_OK(c, hipMemcpy(c->cut_buf.p, &s, sizeof(s), hipMemcpyHostToDevice));
+  }
+  return KGPU_OK;
+}
+
+// processedNodes on a list that holds a node twice.  The reference counts len(filtered) + len(statuses)
+// (generic_scheduler.go:486-487) and `statuses` is a map by node NAME (:465-470): a failing node whose rows
+// were both examined counts once, a fitting one once per row.  The kernels count rows, so after a cycle on
+// an aliased list the surplus rows come off EvaluatedNodes and off the stored nextStartNodeIndex.  The
+// cycle ran on the per-pod launches: status holds a failing row's word, 0 for a kept row and
+// kStatusNotEvaluated for a row the cut left out.
+int alias_processed(kgpu_ctx* c, kgpu_result* res) {
+  const int32_t N = c->st.N;
+  if (c->alias_rows.empty() || N <= 0 || c->comm || c->xg_nranks > 1) return KGPU_OK;
+  SYNC_OK(c);
+  int32_t surplus = 0;
+  for (const auto& kv : c->alias_rows) {
+    int32_t failed = 0;
+    for (int32_t r : kv.second) {
+      if (r < 0 || r >= N) continue;
+      uint32_t w = 0;
+      HIP_OK(c, hipMemcpy(&w, c->st.status + r, sizeof(w), hipMemcpyDeviceToHost));
+      failed += (w != 0 && w != kgpu::kStatusNotEvaluated) ? 1 : 0;
+    }
+    surplus += std::max(failed - 1, 0);
+  }
+  if (surplus == 0) return KGPU_OK;
+  res->evaluated -= surplus;
+  if (!c->cut_init) {  // no list was long enough for a cut yet: the index starts its life here
+    int rc;
+    if ((rc = ensure(c, c->cut_buf, 16))) return rc;
+    HIP_OK(c, hipMemset(c->cut_buf.p, 0, 16));
+    c->cut_init = true;
+  }
+  int32_t s = 0;
+  HIP_OK(c, hipMemcpy(&s, c->cut_buf.p, sizeof(s), hipMemcpyDeviceToHost));
+  s = ((s % N - surplus) % N + N) % N;
+  HIP_OK(c, hipMemcpy(c->cut_buf.p, &s, sizeof(s), hipMemcpyHostToDevice));
+  return KGPU_OK;
+}
+
 // internal: run_batch_once's persistent run aborted before resolving any pod and was the call's only
 // state-changing launch (never returned to a caller)
 constexpr int kCleanAbort = 1000;
@@ -2101,14 +2156,27 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   if (n <= 0) return KGPU_OK;
   int rc;
   fail_point();
-  if (c->has_alias && assume) {
+  if (c->cut_fold && c->st.cut_state == nullptr && (rc = fold_rotation(c))) return rc;
+  if (c->has_alias && !c->in_alias) {
     // A node listed twice: the device assume updates one row only, so place pods one at a time
-    // and apply NodeInfo.AddPod to every row of the chosen node through k_delta.
+    // and apply NodeInfo.AddPod to every row of the chosen node through k_delta.  Every call takes this
+    // loop, with or without assume: alias_processed corrects each cycle's count.
+    struct Nested {
+      kgpu_ctx* c;
+      ~Nested() { c->in_alias = false; }
+    } nested{c};
+    c->in_alias = true;
+    // Each cycle runs on the per-pod launches (diag), which leave every row's status word behind:
+    // alias_processed needs them.
     for (int32_t i = 0; i < n; ++i) {
-      if ((rc = run_batch(c, qs + i, 1, pools, first_seq + i, results + i, stats, diag, 0))) return rc;
+      if ((rc = run_batch(c, qs + i, 1, pools, first_seq + i, results + i, stats, true, 0))) return rc;
+      if ((rc = alias_processed(c, results + i))) return rc;
+      if (!assume) continue;
       if (results[i].node >= 0 && (rc = assume_via_delta(c, qs[i], pools, results[i].node))) return rc;
       if (results[i].node >= 0) drop_nominated(c, qs[i].uid);
     }
+    c->last_diag = diag;
+    c->last_run_all = diag && c->run_all;
     return KGPU_OK;
   }
   if (!c->nom.list.empty()) {
@@ -2841,8 +2909,10 @@ int alloc_node_work(kgpu_ctx* c) {
       c->cut_init = true;
     }
     st.cut_state = static_cast<int32_t*>(c->cut_buf.p);
+    c->cut_fold = false;
   } else {
     st.cut_state = nullptr;
+    c->cut_fold = c->cut_init;
   }
   // math.Log(x) for x = 0 .. n_total + 2 (PodTopologySpread weights, scoring.go:286-288)
   std::vector<double> lt((size_t)st.n_total + 3);
@@ -3465,6 +3535,7 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   const int kidx = kgpu::batch_geometry(c->st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
                                         &per, &groups, c->batch_geo_first);
   if (kidx < 0) return fail(c, KGPU_E_UNSUPPORTED, "no persistent geometry for this node count");
+  if (c->cut_fold && (rc = fold_rotation(c))) return rc;
   // the pools ride on the stream like every other copy (ordered after the batch in flight)
   if ((rc = upload_pools(c, pools))) return rc;
   if (!c->ticket.p) {  // resolve_tail's counters: the top one and 8 group counters, a 64-byte line each

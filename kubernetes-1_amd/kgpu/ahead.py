@@ -55,12 +55,7 @@ class BatchAhead:
         e, self.adopt = self.adopt, None
         if e is None:
             return
-        log = self.cache._log
-        if log and log[0][0] == "add" and log[0][1] == e.host and log[0][2] == e.key:
-            self.cache.engine.adopt_pod(e.slot, self.cache.uid_ids.add(e.key))
-            self.cache.dev_pods[e.key] = e.host
-            del log[0]
-        else:
+        if not self.cache.adopt_assumed(e.slot, e.key, e.host):
             self.spec.appendleft(e)
 
     def _changed(self):

@@ -368,6 +368,21 @@ class SchedulerCache:
         self._last_batch = (batch, keep)
         return self.generation
 
+    def adopt_assumed(self, slot, key, host):
+        """A pod that kgpu_schedule_batch assumed on the device (assumed-pod slot `slot`, Engine.next_slot
+        before the batch plus the placed pods ahead of it) and the scheduler then assumed on the same
+        host (assume_pod): when that assume is the oldest change not yet synced, the device row already
+        holds it, so its UID is adopted (kgpu_adopt_pod) and no ADD_POD is sent.  Later REMOVE_PODs of
+        the pod (forget, expiry, a bind confirmed on another node) then find it by UID.  Returns False,
+        changing nothing, when the oldest unsynced change is anything else."""
+        log = self._log
+        if not (log and log[0][0] == "add" and log[0][1] == host and log[0][2] == key):
+            return False
+        self.engine.adopt_pod(slot, self.uid_ids.add(key))
+        self.dev_pods[key] = host
+        del log[0]
+        return True
+
     # ------------------------------------------------------------------ cycles
     def schedule(self, pod, seq=0):
         """One scheduling cycle on the synced mirror (no assume: the caller assumes through

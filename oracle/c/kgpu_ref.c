@@ -1321,6 +1321,10 @@ int kgpu_ref_schedule(ref_state* r, const kgpu_pod_query* qs, int nq, const kgpu
       evaluated = p;
     } else {
       for (int i = 0; i < N; ++i) if (status[i] == 0) feasible[nf++] = i;
+      /* no cut: processedNodes is the whole list, so the stored index is only folded into it --
+       * (nextStartNodeIndex + N) % N (generic_scheduler.go:487).  It matters after the list shrank
+       * below a stored index: the next cycle under a cut starts from the folded value. */
+      if (r->total == N && N > 0) r->next_start %= N;
     }
     kgpu_result res;
     memset(&res, 0, sizeof(res));
@@ -1395,6 +1399,16 @@ int kgpu_ref_schedule(ref_state* r, const kgpu_pod_query* qs, int nq, const kgpu
             "score (parallel) %.1f, normalize+totals+selectHost+assume %.1f\n", r->threads, ph[0] / nq, ph[1] / nq,
             ph[2] / nq, ph[3] / nq, ph[4] / nq);
 #undef PHASE
+  return 0;
+}
+
+/* nextStartNodeIndex lives with the generic scheduler, not with the snapshot: a caller that rebuilds the
+ * reference on a new snapshot carries it over.  Stored unreduced; every cycle takes it mod N. */
+int kgpu_ref_get_next_start(const ref_state* r) { return r->next_start; }
+
+int kgpu_ref_set_next_start(ref_state* r, int next_start) {
+  if (next_start < 0) return -1;
+  r->next_start = next_start;
   return 0;
 }
 

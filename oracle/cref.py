@@ -31,6 +31,8 @@ def lib():
         L.kgpu_ref_schedule.argtypes = [vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, vp]
         L.kgpu_ref_read_nodes.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.kgpu_ref_broken_linear.argtypes = [vp, vp, C.c_int, vp]
+        L.kgpu_ref_get_next_start.argtypes = [vp]
+        L.kgpu_ref_set_next_start.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -62,6 +64,17 @@ class RefEngine:
 
     def __del__(self):
         self.close()
+
+    @property
+    def next_start(self):
+        """nextStartNodeIndex as stored (the value of the node count it was last used with; a cycle
+        takes it mod N).  Assignable: the rotation belongs to the scheduler, not to the snapshot."""
+        return int(lib().kgpu_ref_get_next_start(self.h))
+
+    @next_start.setter
+    def next_start(self, value):
+        if lib().kgpu_ref_set_next_start(self.h, int(value)):
+            raise ValueError("nextStartNodeIndex %r" % (value,))
 
     def schedule(self, queries, pools, first_seq=0, diag=False):
         from kgpu import abi

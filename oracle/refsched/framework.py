@@ -303,9 +303,11 @@ class GenericScheduler:
         index = {NI.name(ni.node): i for i, ni in enumerate(all_nodes)}
         to_find = self.num_feasible_nodes_to_find(len(all_nodes))
         feasible, statuses = [], {}
+        rows = []  # the list position of each feasible entry: a node listed twice is two candidates of selectHost
         if not self.fw.filters:
             # no filter plugins: the first numNodesToFind nodes, not rotated (generic_scheduler.go:438-444)
             feasible = [ni.node for ni in all_nodes[:to_find]]
+            rows = list(range(len(feasible)))
         else:
             # checkNode (generic_scheduler.go:451-471) run by one worker: after to_find nodes fit, the
             # next node that fits cancels the search and is dropped (length > numNodesToFind); failures
@@ -325,6 +327,7 @@ class GenericScheduler:
                     if len(feasible) >= to_find:
                         break
                     feasible.append(ni.node)
+                    rows.append((self.next_start + i) % len(all_nodes))
                 else:
                     statuses[NI.name(ni.node)] = (plugin, fst)
         processed = len(feasible) + len(statuses)
@@ -345,7 +348,7 @@ class GenericScheduler:
             totals = []
             for i, n in enumerate(feasible):
                 totals.append([NI.name(n), sum(scores[k][i][1] for k in scores)])
-        host, hidx = select_host(totals, index, self.fw.profile, pod_seq)
+        host, hidx = select_host(totals, index, self.fw.profile, pod_seq, rows=rows)
         return Result(host, hidx, len(feasible) + len(statuses), len(feasible), statuses, scores, totals,
                       [NI.name(n) for n in feasible])
 
@@ -365,26 +368,36 @@ def pod_passes_basic_checks(pod, pvcs):
             raise ScheduleError('persistentvolumeclaim "%s" is being deleted' % claim)
 
 
-def select_host(totals, index, profile, pod_seq):
-    """selectHost (generic_scheduler.go:217-238) with the deterministic packed-key tie-break."""
+def select_host(totals, index, profile, pod_seq, rows=None):
+    """selectHost (generic_scheduler.go:217-238) with the deterministic packed-key tie-break.
+
+    rows: the Snapshot.List() position of each entry of `totals`.  The reference samples over the
+    entries, so a node that UpdateSnapshot listed twice takes part twice; the packed key ranks an entry
+    by its own list position (on a list without duplicates that is index[name])."""
     if not totals:
         raise ScheduleError("empty priorityList")
-    best_key, best = -1, None
-    for name, score in totals:
-        k = tiebreak.key(score, index[name], pod_seq, profile.seed, profile.tie_break_mode)
+    best_key, best, best_row = -1, None, -1
+    for i, (name, score) in enumerate(totals):
+        row = index[name] if rows is None else rows[i]
+        k = tiebreak.key(score, row, pod_seq, profile.seed, profile.tie_break_mode)
         if k > best_key:
-            best_key, best = k, name
-    return best, index[best]
+            best_key, best, best_row = k, name, row
+    return best, best_row
 
 
 def schedule_sequence(nodes, existing_pods, pods, profile, services=(), rcs=(), rss=(), sss=(),
-                      first_seq=0, pvcs=(), order="tree", image_nodes=None):
+                      first_seq=0, pvcs=(), order="tree", image_nodes=None, next_start=0, state=None):
     """scheduleOne loop: each placed pod is assumed (NodeInfo.AddPod) before the next one.
+
+    next_start: nextStartNodeIndex the scheduler brings along from earlier cycles on another snapshot
+    (stored unreduced, taken mod the list length on use).  state: a dict that receives the scheduler's
+    "next_start" after the last pod and the "snapshot" with the placed pods assumed.
 
     Returns a list of Result (or FitError/ScheduleError instances for unschedulable pods)."""
     snap = NI.Snapshot(nodes, existing_pods, order=order, image_nodes=image_nodes)
     fw = Framework(profile, Handle(snap, services, rcs, rss, sss, pvcs))
     gs = GenericScheduler(fw)
+    gs.next_start = next_start
     out = []
     for i, pod in enumerate(pods):
         try:
@@ -397,4 +410,7 @@ def schedule_sequence(nodes, existing_pods, pods, profile, services=(), rcs=(), 
         placed["spec"]["nodeName"] = r.host
         snap.get(r.host).add_pod(placed)
         out.append(r)
+    if state is not None:
+        state["next_start"] = gs.next_start
+        state["snapshot"] = snap
     return out

@@ -138,9 +138,9 @@ def _pod_terms(pod):
 SEL_EMPTY = 2  # kSelEmpty (kgpu_internal.h): no Service / ReplicaSet selects the pod
 
 
-@functools.lru_cache(maxsize=None)
-def _topo_kinds(seed):
-    """(planned, loose, free) of the topo family's batch pods, from the objects, the compiled queries and the calls.
+def _topo_kinds_of(existing, pods, c):
+    """(planned, loose, free) of the batch pods among `pods`, from the objects, the compiled queries c.q and the
+    calls c.calls; `existing` are the pods the engine holds before the first call.
     planned: the pod has terms of its own that k_tbatch carries (a topology plan for certain, t_add accepts it).
     loose: no terms of its own and no Service / ReplicaSet selects it (an upper bound of the pods without a plan).
     free: loose, and no (anti-)affinity term the engine knows by then matches it -- those of the existing pods
@@ -148,13 +148,12 @@ def _topo_kinds(seed):
     before it matches them): certainly no topology plan, so it belongs to k_cbatch / k_nbatch / the per-pod
     launches."""
     from kgpu.compile import label_selector_matches
-    _, existing, pods, _, _ = gen_random.family("topo", seed)
-    c = _case("topo", seed, _cut_pct("topo"))
     topo = _topo(c)
     in_batch = np.zeros(len(pods), bool)
     free = np.zeros(len(pods), bool)
     seen = [t for p in existing for t in _pod_terms(p)]
-    for (lo, hi), call in zip(c._spans(), c.calls):
+    spans = [(call[1], call[2]) if call[0] == "batch" else (call[1], call[1] + 1) for call in c.calls]
+    for (lo, hi), call in zip(spans, c.calls):
         seen += [t for p in pods[lo:hi] for t in _pod_terms(p)]
         if call[0] != "batch":
             continue
@@ -166,6 +165,39 @@ def _topo_kinds(seed):
     loose = in_batch & ~topo & (c.q["dpts"]["kind"] == SEL_EMPTY)
     planned = in_batch & topo & ~np.array([_t_add_refuses(p) for p in pods])
     return planned, loose, free & loose
+
+
+@functools.lru_cache(maxsize=None)
+def _topo_kinds(seed):
+    """_topo_kinds_of the topo family's seed."""
+    _, existing, pods, _, _ = gen_random.family("topo", seed)
+    return _topo_kinds_of(existing, pods, _case("topo", seed, _cut_pct("topo")))
+
+
+def _topo_counts(planned, loose, free, need):
+    """What _topo_bounds holds the counters to; dicts of several batches add up field by field."""
+    return {"planned": int(planned.sum()), "loose": int(loose.sum()), "loose_plain": int((loose & ~need).sum()),
+            "loose_need": int((loose & need).sum()), "free_plain": int((free & ~need).sum()),
+            "free_need": int((free & need).sum())}
+
+
+def _topo_bounds(want, opts, cut, tot, n, batch_pods, refusal):
+    """The topology family's bounds on the counter totals `tot` of batches whose pods count as `n` (_topo_counts)."""
+    n_c, n_n = n["free_plain"], n["free_need"]  # certain to reach k_cbatch / k_nbatch
+    nb = opts in ("norm1", "norm4")
+    if cut:
+        want(tot["cut_topo_persistent_pods"] > 0, "no cut-mode k_tbatch run", tot)
+        want(tot["cut_topo_persistent_pods"] >= n["planned"], "topology pods outside k_tbatch", tot, n["planned"])
+        if opts == "norm4":  # a k_nbatch run may absorb a constant-maxima pod
+            both = tot["cut_persistent_pods"] + tot["norm_persistent_pods"]
+            want(n_c + n_n <= both <= n["loose"], "k_cbatch + k_nbatch pods", tot, n_c, n_n)
+        else:
+            want(n_c <= tot["cut_persistent_pods"] <= n["loose_plain"], "k_cbatch pods", tot, n_c)
+    if nb:
+        most = n["loose_need"] if opts == "norm1" else n["loose"]
+        want(n_n <= tot["norm_persistent_pods"] <= most, "k_nbatch pods", tot, n_n)
+        if refusal:
+            want(tot["persistent_pods"] < batch_pods, "no pod left the batch for the per-pod pipeline", tot, batch_pods)
 
 
 # ---------------------------------------------------------------- CPU
@@ -343,8 +375,10 @@ def _check_records(case, got, rows, what):
         raise AssertionError("%s\n%s" % (_describe(case, got, rows, what), e)) from None
 
 
-def _routing(fam, seed, pct, opts, case, deltas):
-    """The routing assertions, as a list of failures (reported after the records, which say more)."""
+def _routing(fam, seed, pct, opts, case, deltas, topo_sum=None):
+    """The routing assertions, as a list of failures (reported after the records, which say more).
+    topo_sum: a dict of a caller that holds the topology family's bounds over several _routing calls itself
+    (_topo_bounds; test_delta_routing, one call per checkpoint): the counter totals are added to it instead."""
     bad = []
 
     def want(cond, *msg):
@@ -396,22 +430,12 @@ def _routing(fam, seed, pct, opts, case, deltas):
             if opts == "default":
                 want(d["persistent_pods"] == hi - lo - n_need, "default: persistent pods != constant-maxima pods", n_need, call, d)
     if fam == "topo" and opts != "perpod":
-        planned, loose, free = _topo_kinds(seed)
-        n_c, n_n = int((free & ~need).sum()), int((free & need).sum())  # certain to reach k_cbatch / k_nbatch
-        nb = opts in ("norm1", "norm4")
-        if cut:
-            want(tot["cut_topo_persistent_pods"] > 0, "no cut-mode k_tbatch run", tot)
-            want(tot["cut_topo_persistent_pods"] >= int(planned.sum()), "topology pods outside k_tbatch", tot, int(planned.sum()))
-            if opts == "norm4":  # a k_nbatch run may absorb a constant-maxima pod
-                both = tot["cut_persistent_pods"] + tot["norm_persistent_pods"]
-                want(n_c + n_n <= both <= int(loose.sum()), "k_cbatch + k_nbatch pods", tot, n_c, n_n)
-            else:
-                want(n_c <= tot["cut_persistent_pods"] <= int((loose & ~need).sum()), "k_cbatch pods", tot, n_c)
-        if nb:
-            most = int((loose & need).sum()) if opts == "norm1" else int(loose.sum())
-            want(n_n <= tot["norm_persistent_pods"] <= most, "k_nbatch pods", tot, n_n)
-            if seed == REFUSAL_SEED:
-                want(tot["persistent_pods"] < batch_pods, "no pod left the batch for the per-pod pipeline", tot, batch_pods)
+        if topo_sum is not None:
+            for k in tot:
+                topo_sum[k] = topo_sum.get(k, 0) + tot[k]
+            topo_sum["batch_pods"] = topo_sum.get("batch_pods", 0) + batch_pods
+        else:
+            _topo_bounds(want, opts, cut, tot, _topo_counts(*_topo_kinds(seed), need), batch_pods, seed == REFUSAL_SEED)
     print("routing %s seed %d pct %d %s: %s of %d batch pods" % (fam, seed, pct, opts, tot, batch_pods))
     return bad
 
