@@ -22,7 +22,8 @@ type metav1LabelSelector = metav1.LabelSelector
 var unsafeSizeofSnapshot = unsafe.Sizeof(C.kgpu_snapshot{})
 
 
-// argsFrom decodes the GpuEval pluginConfig args (INTEGRATION.md section 4).
+// argsFrom decodes the GpuEval pluginConfig args (INTEGRATION.md section 4); booleans such as
+// runAllFilters and cutTopoOnePod default to false.
 func argsFrom(obj runtime.Object) (*profileArgs, error) {
 	p := &profileArgs{HardPodAffinityWeight: 1, PercentageOfNodesToScore: 100, Mode: "select", TieBreakSeed: 0x7B,
 		LeastResources: map[string]int64{"cpu": 1, "memory": 1}, MostResources: map[string]int64{"cpu": 1, "memory": 1},

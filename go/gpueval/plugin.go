@@ -65,6 +65,11 @@ type profileArgs struct {
 	// filter plugin runs on every node and Filter returns the merged status with every failing
 	// plugin's reasons (KGPU_OPT_RUN_ALL_FILTERS).  Set it together with that Policy field.
 	RunAllFilters          bool
+	// CutTopoOnePod ("cutTopoOnePod": true): with PercentageOfNodesToScore below 100, a cycle of a pod with
+	// topology state runs as a one-pod launch of the persistent topology kernel's cut-mode instantiation
+	// instead of the per-pod topology pipeline (KGPU_OPT_CUT_TOPO_ONE, off by default; same record, status
+	// words and scores of the kept nodes).
+	CutTopoOnePod          bool
 	ignoredResources       map[string]struct{}
 }
 
@@ -252,6 +257,13 @@ func (g *GpuEval) upload(list []*framework.NodeInfo, a *arena) error {
 		}
 		if g.prof.RunAllFilters {
 			if err := eng.setOption(C.KGPU_OPT_RUN_ALL_FILTERS, 1); err != nil {
+				eng.close()
+				c.close()
+				return err
+			}
+		}
+		if g.prof.CutTopoOnePod {
+			if err := eng.setOption(C.KGPU_OPT_CUT_TOPO_ONE, 1); err != nil {
 				eng.close()
 				c.close()
 				return err

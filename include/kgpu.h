@@ -728,6 +728,21 @@ int kgpu_read_nodes(kgpu_ctx* ctx, int64_t* req_cpu, int64_t* req_mem, int64_t* 
  * way; read at launch.  The environment variable KGPU_BATCH_EARLY_PUBLISH=0|1 sets a new engine's initial
  * value (measurement of unmodified callers). */
 #define KGPU_OPT_BATCH_EARLY_PUBLISH 27
+/* KGPU_OPT_CUT_TOPO_ONE (28): 0 (default) = with percentageOfNodesToScore below 100, a kgpu_schedule_one
+ * cycle of a topology pod takes the per-pod topology pipeline (k_topo_*, k_cut, k_topo_reg); 1 = it runs as a
+ * one-pod launch of k_tbatch's cut-mode instantiation (every geometry and profile row; the cycle's tables,
+ * zeroed granules and completion word ride in the short cycle's single copy, the resident topology state of
+ * KGPU_OPT_TOPO_RESIDENT is used and written back).  Needs KGPU_OPT_CUT_TOPO_PERSISTENT 1.
+ * Cycles under KGPU_OPT_RUN_ALL_FILTERS, nominated cycles, node-sharded engines, an aliased node list,
+ * KGPU_OPT_TOPO_PERSISTENT 0, clusters with more than 64 node label keys, pods the persistent topology kernel
+ * does not plan (a DoNotSchedule constraint on a node-unique key) and cycles of pods without topology state
+ * keep the per-pod pipeline either way.  The two paths return the same record and the same kgpu_get_filter
+ * words, and the same kgpu_get_scores rows on the kept nodes (word 0); on every other node the one-pod run
+ * leaves 0, as this header promises.  nextStartNodeIndex advances with and without assume, and stays continuous
+ * with every other path.  KGPU_OPT_HOLD_GROUP and KGPU_OPT_ABORT_AT are honoured as in k_tbatch.  The
+ * environment variable KGPU_CUT_TOPO_ONE=0|1 sets a new engine's initial value (measurement of unmodified
+ * callers). */
+#define KGPU_OPT_CUT_TOPO_ONE 28
 int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
 /* Engine counters: out[0] = calls issued again with a cooperative launch after a persistent run's
  * workgroups were not all resident before its first pod (KGPU_OPT_COOPERATIVE); out[1] = persistent
@@ -738,7 +753,9 @@ int kgpu_set_option(kgpu_ctx* ctx, int32_t option, int64_t value);
  * cut-mode persistent topology launches (KGPU_OPT_CUT_TOPO_PERSISTENT; k_tbatch pods only, as out[5] counts
  * k_cbatch pods only); out[7] = pods resolved inside normalize-pass persistent launches
  * (KGPU_OPT_NORM_PERSISTENT; k_nbatch pods, at pct = 100 and under a cut; they also count in out[1] and in
- * kgpu_debug_instantiation's out[3], not in out[5]).  Returns how many counters exist. */
+ * kgpu_debug_instantiation's out[3], not in out[5]); out[8] = kgpu_schedule_one cycles resolved inside one-pod
+ * cut-mode persistent topology launches (KGPU_OPT_CUT_TOPO_ONE; they also count in out[1] and in
+ * kgpu_debug_instantiation's out[3], not in out[6], which stays batch pods).  Returns how many counters exist. */
 int kgpu_debug_counters(const kgpu_ctx* ctx, int64_t* out, int32_t n);
 /* Pure host, no context: the geometry the engine would pick.  kernel 1 = k_batch, 2 = k_tbatch;
  * first = KGPU_OPT_*_GEO value.  Returns the geometry index (>= 0) and fills out[0..3] = threads per

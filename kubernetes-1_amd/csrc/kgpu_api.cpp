@@ -275,6 +275,8 @@ struct kgpu_ctx {
   int32_t norm_persistent = 0;      // KGPU_OPT_NORM_PERSISTENT: 0 off, v >= 1 the absorb window of a k_nbatch run
   int64_t n_norm_pods = 0;          // kgpu_debug_counters: pods resolved inside k_nbatch launches
   int64_t n_cut_topo_pods = 0;      // kgpu_debug_counters: pods resolved inside cut-mode persistent topology launches
+  bool cut_topo_one = false;        // KGPU_OPT_CUT_TOPO_ONE
+  int64_t n_cut_topo_one = 0;       // kgpu_debug_counters: cycles resolved inside one-pod cut-mode topology runs
   DevBuf cgran;                     // cut-mode persistent runs: count and key granules, position words
   int64_t n_cut_pods = 0;           // kgpu_debug_counters: pods resolved inside cut-mode persistent launches
   bool tbatch_wlab = true;          // KGPU_OPT_TBATCH_WLAB
@@ -1839,7 +1841,7 @@ int run_tbatch(kgpu_ctx* c, TRun& tr, int first, int count, int64_t first_seq, i
   ++c->state_launches;
   note_geometry(c, 2, geo, groups, per);
   note_instantiation(c, kgpu::tbatch_row(c->spec, a.def_res != 0), xg, false, count);
-  if (cut) c->n_cut_topo_pods += count;
+  if (cut) (diag ? c->n_cut_topo_one : c->n_cut_topo_pods) += count;  // a diagnostic run is one pod
   if (kgpu::launch_tbatch(dst, a, groups, geo, c->spec, xg, coop, c->stream, cut))
     return fail(c, KGPU_E_DEVICE, std::string("k_tbatch launch failed: ") + hipGetErrorString(hipGetLastError()));
   if (c->ar.on) ht(c, 7);  // 7: the launch (API call)
@@ -2356,6 +2358,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   bool used_persistent = false;
   int64_t cut_pods = 0;  // this call's pods inside cut-mode runs (taken back when the call is issued again)
   int64_t cut_topo_pods = 0;  // ... and inside cut-mode persistent topology runs
+  int64_t cut_topo_one = 0;   // ... and inside one-pod cut-mode topology runs (diagnostic cycles)
   int64_t norm_pods = 0;      // ... and inside normalize-pass persistent runs (k_nbatch)
   // KGPU_OPT_NORM_PERSISTENT: pods that need the normalize pass and carry no topology state go through
   // k_nbatch (unsharded batch runs; the profile row must hold a normalized plugin and the raw taint maximum,
@@ -2378,9 +2381,11 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
   // a diagnostic cycle (kgpu_schedule_one: status words and per-plugin scores) of one topology pod
   // runs as a one-pod persistent run too
   // under a cut (percentageOfNodesToScore < 100) batch runs take its cut-mode instantiation
-  // (KGPU_OPT_CUT_TOPO_PERSISTENT); diagnostic cycles keep the per-pod pipeline (k_cut)
+  // (KGPU_OPT_CUT_TOPO_PERSISTENT); diagnostic cycles keep the per-pod pipeline (k_cut) unless
+  // KGPU_OPT_CUT_TOPO_ONE sends them through a one-pod cut-mode run (not the aliased-list loop's cycles)
   const int tgeo = (topo_on && c->tfast && (!diag || (n == 1 && !st.run_all)) && (!sharded || xg) &&
-                    (!cut || (c->cut_topo_persistent && !diag)) && !nom_dev && st.K <= 64)
+                    (!cut || (c->cut_topo_persistent && (!diag || (c->cut_topo_one && !c->in_alias)))) && !nom_dev &&
+                    st.K <= 64)
                        ? kgpu::tbatch_geometry(st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
                                                &tper, &tgroups, c->tbatch_geo_first)
                        : -1;
@@ -2407,7 +2412,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
         if ((rc = run_tbatch(c, tr, i, j - i, first_seq, assume, tper, tgroups, tgeo, tb_arena ? nullptr : abort_word, xg,
                              diag, cut)))
           return rc;
-        if (cut) cut_topo_pods += j - i;
+        if (cut) (diag ? cut_topo_one : cut_topo_pods) += j - i;
         // the one-pod run's last workgroup copies the abort word into pinned memory after everything is
         // written back: the call's completion word
         done_word = (c->tb_abort_mapped && !c->timing && !c->phase_trace)
@@ -2795,6 +2800,7 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     for (int k = 0; k < 2; ++k) c->tc.dirty[k] = c->tc.buf[k].bytes;
     c->n_cut_pods -= cut_pods;
     c->n_cut_topo_pods -= cut_topo_pods;
+    c->n_cut_topo_one -= cut_topo_one;
     c->n_norm_pods -= norm_pods;
     return kCleanAbort;
   }
@@ -3844,6 +3850,7 @@ int kgpu_create(const kgpu_config* cfg, kgpu_ctx** out) try {
   }
   if (const char* e = std::getenv("KGPU_HOST_TRACE")) c->htrace = e[0] == '1';
   if (const char* e = std::getenv("KGPU_BATCH_EARLY_PUBLISH")) c->batch_early = e[0] != '0';
+  if (const char* e = std::getenv("KGPU_CUT_TOPO_ONE")) c->cut_topo_one = e[0] == '1';
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
     return KGPU_E_DEVICE;
   hipDeviceProp_t prop;
@@ -3998,10 +4005,10 @@ int kgpu_read_phase_trace(kgpu_ctx* c, int64_t* out, int32_t max_pods) try {
 
 int kgpu_debug_counters(const kgpu_ctx* c, int64_t* out, int32_t n) {
   if (!c || (n > 0 && !out)) return KGPU_E_INVAL;
-  const int64_t v[8] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
-                        c->n_cut_pods, c->n_cut_topo_pods, c->n_norm_pods};
-  for (int32_t i = 0; i < n && i < 8; ++i) out[i] = v[i];
-  return 8;
+  const int64_t v[9] = {c->n_coop_retry, c->n_persist, c->n_coop, c->n_class_init, c->n_pod_table_full,
+                        c->n_cut_pods, c->n_cut_topo_pods, c->n_norm_pods, c->n_cut_topo_one};
+  for (int32_t i = 0; i < n && i < 9; ++i) out[i] = v[i];
+  return 9;
 }
 
 int kgpu_geometry_for(int32_t kernel, int32_t n_nodes, int32_t max_groups, int32_t first, int32_t out[4]) try {
@@ -4091,6 +4098,7 @@ int kgpu_set_option(kgpu_ctx* c, int32_t option, int64_t value) try {
   else if (option == KGPU_OPT_HOLD_GROUP) c->hold_group = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else if (option == KGPU_OPT_CUT_PERSISTENT) c->cut_persistent = value != 0;
   else if (option == KGPU_OPT_CUT_TOPO_PERSISTENT) c->cut_topo_persistent = value != 0;
+  else if (option == KGPU_OPT_CUT_TOPO_ONE) c->cut_topo_one = value != 0;
   else if (option == KGPU_OPT_NORM_PERSISTENT) c->norm_persistent = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), INT32_MAX);
   else if (option == KGPU_OPT_SKIP_RELEASE_AT) c->skip_release_at = value < 0 || value > INT32_MAX ? -1 : (int32_t)value;
   else return KGPU_E_INVAL;

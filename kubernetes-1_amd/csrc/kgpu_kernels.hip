@@ -4446,6 +4446,10 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     int32_t zone[kStream ? K : 1];  // streamed rows: the row's zone, for the normalize pass
     uint32_t sf = 0, smaxT = 0, smaxNA = 0, snon = 0, sadjmin = 0xFFFFFFFFu, sadjmax = 0, sdmax = 0, szoned = 0;
     int64_t simin = INT64_MAX, simax = INT64_MIN;
+    // CUT, diagnostic cycles: nextStartNodeIndex before this pod (thread 0 advances C.s before the pod's last
+    // barrier) and the lane's feasible rows beyond the cut (bit j)
+    [[maybe_unused]] int cut_se = 0;
+    [[maybe_unused]] uint32_t cut_lost = 0;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const int n = lo + j * B + tid;
@@ -4503,6 +4507,7 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
       // ---- round 0: feasible counts at or above s and below s, every workgroup sums the row (k_cbatch)
       TCutShared& C = *reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut);
       const int se = ta.cut_nofilt ? 0 : C.s, KF = st.to_find;
+      cut_se = se;
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const int n = lo + j * B + tid;
@@ -4561,6 +4566,7 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
                          (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) + 1;
         if (f && rank == KF + 1) C.pown = hi ? n - se : n + st.N - se;
         feas[j] = f && rank <= KF;
+        if (ta.diag && f && !feas[j]) cut_lost |= 1u << j;
         if (!feas[j]) continue;
         ++sf;
         smaxT = max(smaxT, (uint32_t)o[j].taint);
@@ -4995,6 +5001,44 @@ __global__ __launch_bounds__(B) void k_tbatch(const DevState* __restrict__ stp, 
     if constexpr (CUT) {  // every workgroup advances the rotation (read again after the pod's last barrier)
       TCutShared& C = *reinterpret_cast<TCutShared*>(lds_raw + ta.o_cut);
       if (tid == 0) C.s = (C.s + C.rp) % st.N;
+      // A diagnostic cycle under the cut (KGPU_OPT_CUT_TOPO_ONE): findNodesThatPassFilters
+      // stopped at rotated position p (C.rp, read after the barrier above), so a node that was not kept and
+      // lies at pos >= p was never examined -- the feasible rows beyond the cut (cut_lost; rank to_find + 1
+      // sits at p, the later ranks behind it) and the failing rows there; a failing row below p keeps its
+      // word.  p = N when nothing was cut: no pos reaches it.  cut_nofilt: se = 0 and p = to_find.  The rows
+      // of a node that was not kept are 0, as is every row of an unscored cycle (one feasible node, or
+      // KGPU_Q_SCORE_ERROR).  Direct stores: this lane stored the word and the rows earlier in the pod.
+      if (ta.diag) {
+        const int p = C.rp;
+        const bool unscored = !(placed && feas_total >= 2);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          const int n = lo + j * B + tid;
+          if (n >= st.N) continue;
+          const int pos = n >= cut_se ? n - cut_se : n + st.N - cut_se;
+          const bool never = !feas[j] && pos >= p, lost = ((cut_lost >> j) & 1u) != 0;
+          if constexpr (kDefer) {
+            if (never) dstat = KGPU_FS_NOT_EVALUATED;
+            if (lost || unscored) {
+#pragma unroll
+              for (int k = 0; k < KGPU_NUM_SCORES; ++k) dv[k] = 0;
+#pragma unroll
+              for (int k = 0; k < 5; ++k) dn[k] = 0;
+#pragma unroll
+              for (int k = 0; k < 3; ++k) dt[k] = 0;
+            }
+          } else {
+            if (never) gp(st.status)[n] = KGPU_FS_NOT_EVALUATED;
+            if (lost || (unscored && feas[j])) {
+              for (int si = 0; si < st.n_scores; ++si) {
+                const int sc = cp(st.scores)[si];
+                gp(st.diag_raw)[(size_t)sc * st.N + n] = 0;
+                gp(st.diag_norm)[(size_t)sc * st.N + n] = 0;
+              }
+            }
+          }
+        }
+      }
     }
     if (placed && ta.assume) {
       const int wl = wnode - st.node_base;

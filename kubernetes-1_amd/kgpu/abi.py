@@ -29,6 +29,7 @@ OPT_CUT_PERSISTENT = 24
 OPT_CUT_TOPO_PERSISTENT = 25
 OPT_NORM_PERSISTENT = 26
 OPT_BATCH_EARLY_PUBLISH = 27
+OPT_CUT_TOPO_ONE = 28
 CODE_SUCCESS, CODE_ERROR, CODE_UNSCHEDULABLE, CODE_UNRESOLVABLE = 0, 1, 2, 3
 STATUS_NOT_EVALUATED = 0xFF  # KGPU_FS_NOT_EVALUATED: percentageOfNodesToScore stopped before the node
 

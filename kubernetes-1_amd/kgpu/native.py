@@ -369,13 +369,14 @@ class Engine:
 
     def counters(self):
         """kgpu_debug_counters: {coop_retries, persistent_launches, coop_launches, class_inits,
-        pod_table_full_uploads, cut_persistent_pods, cut_topo_persistent_pods, norm_persistent_pods}."""
-        out = np.zeros(8, np.int64)
+        pod_table_full_uploads, cut_persistent_pods, cut_topo_persistent_pods, norm_persistent_pods,
+        cut_topo_one_cycles}."""
+        out = np.zeros(9, np.int64)
         n = lib().kgpu_debug_counters(self.h, out.ctypes.data, len(out))
         if n < 0:
             self._check(n)
         return dict(zip(["coop_retries", "persistent_launches", "coop_launches", "class_inits", "pod_table_full_uploads",
-                         "cut_persistent_pods", "cut_topo_persistent_pods", "norm_persistent_pods"],
+                         "cut_persistent_pods", "cut_topo_persistent_pods", "norm_persistent_pods", "cut_topo_one_cycles"],
                         [int(x) for x in out[:n]]))
 
     def broken_linear(self, points, utilizations):

@@ -25,6 +25,11 @@ def main():
                          "classes at upload); 0: each class is met on its first cycle")
     ap.add_argument("--per-pod-pools", type=int, default=0,
                     help="1: every pod compiled on its own, with its own pools block (the Go shim's shape)")
+    ap.add_argument("--pct", type=int, default=100,
+                    help="the profile's percentageOfNodesToScore (0: the reference's adaptive default)")
+    ap.add_argument("--cut-topo-one", type=int, choices=[0, 1], default=None,
+                    help="KGPU_OPT_CUT_TOPO_ONE (default: the library's, 0): with --pct below 100, a topology pod's "
+                         "cycle as a one-pod cut-mode k_tbatch run (tools/cut_one_bench.py alternates the two)")
     args = ap.parse_args()
     from kgpu import cluster
     from kgpu.framework import GpuFramework
@@ -36,6 +41,7 @@ def main():
         nodes, existing, pods, prof = cluster.taints_affinity_spread(n_nodes=args.nodes, n_pods=args.pods)
     else:
         nodes, existing, pods, prof = cluster.pod_affinity(n_nodes=args.nodes, n_existing=args.nodes, n_pods=args.pods)
+    prof.percentage_of_nodes_to_score = args.pct
     fw = GpuFramework(prof, nodes, existing, pods_hint=pods[:16])
     q, pc, _, errs = fw.compile_pods(pods)
     assert not errs
@@ -43,6 +49,9 @@ def main():
     if args.zc is not None:
         from kgpu import abi
         eng.set_option(abi.OPT_ZEROCOPY_POOLS, args.zc)
+    if args.cut_topo_one is not None:
+        from kgpu import abi
+        eng.set_option(abi.OPT_CUT_TOPO_ONE, args.cut_topo_one)
     for i in range(20):  # warm
         eng.schedule_one(q[i], pc, seq=i, assume=False)
     if args.prepare:
@@ -55,8 +64,9 @@ def main():
         eng.schedule_one(qi, pci, seq=i, assume=True)
         lat.append((time.perf_counter() - t) * 1e6)
     la = np.array(lat)
-    print("kgpu_schedule_one config %s %d nodes%s%s: p50 %.1f us, p99 %.1f us, mean %.1f us"
-          % (args.config, args.nodes, " (classes prepared)" if args.prepare else "",
+    print("kgpu_schedule_one config %s %d nodes%s%s%s: p50 %.1f us, p99 %.1f us, mean %.1f us"
+          % (args.config, args.nodes, "" if args.pct == 100 else " pct %d" % args.pct,
+             " (classes prepared)" if args.prepare else "",
              " (per-pod pools)" if args.per_pod_pools else "", np.percentile(la, 50),
              np.percentile(la, 99), la.mean()))
     eng.close()
