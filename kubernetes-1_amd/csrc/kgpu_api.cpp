@@ -34,6 +34,7 @@
 
 #include "kgpu_internal.h"
 #include "kgpu_staging.h"
+#include "kgpu_route.h"
 #include "kgpu_reasons.h"
 
 // ---- RCCL, loaded on first use.  Only node sharding (kgpu_comm_unique_id / kgpu_comm_init) needs
@@ -2148,149 +2149,281 @@ int alias_processed(kgpu_ctx* c, kgpu_result* res) {
   return KGPU_OK;
 }
 
+// ---------------------------------------------------------------- one scheduling call
+// run_batch_once drives a call-local Cycle through staging, one issuer per route (kgpu_route.h decides
+// which) and completion; DESIGN.md "Batch routing" has the table.
+
 // internal: run_batch_once's persistent run aborted before resolving any pod and was the call's only
 // state-changing launch (never returned to a caller)
 constexpr int kCleanAbort = 1000;
 
-int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_pools* pools, int64_t first_seq,
-                   kgpu_result* results, kgpu_stats* stats, bool diag, int32_t assume) {
-  if (!c->uploaded) return fail(c, KGPU_E_STATE, "no snapshot uploaded");
-  if (n <= 0) return KGPU_OK;
+using kgpu_route::PodKind;
+using kgpu_route::Route;
+
+// Workgroups a persistent kernel may use: one per CU at most (KGPU_OPT_MAX_GROUPS lowers it).
+int persistent_groups(const kgpu_ctx* c) {
+  return std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256);
+}
+
+// resolve_tail's counters: the top one and 8 group counters, a 64-byte line each
+int ensure_ticket(kgpu_ctx* c) {
+  if (c->ticket.p) return KGPU_OK;
   int rc;
-  fail_point();
-  if (c->cut_fold && c->st.cut_state == nullptr && (rc = fold_rotation(c))) return rc;
-  if (c->has_alias && !c->in_alias) {
-    // A node listed twice: the device assume updates one row only, so place pods one at a time
-    // and apply NodeInfo.AddPod to every row of the chosen node through k_delta.  Every call takes this
-    // loop, with or without assume: alias_processed corrects each cycle's count.
-    struct Nested {
-      kgpu_ctx* c;
-      ~Nested() { c->in_alias = false; }
-    } nested{c};
-    c->in_alias = true;
-    // Each cycle runs on the per-pod launches (diag), which leave every row's status word behind:
-    // alias_processed needs them.
-    for (int32_t i = 0; i < n; ++i) {
-      if ((rc = run_batch(c, qs + i, 1, pools, first_seq + i, results + i, stats, true, 0))) return rc;
-      if ((rc = alias_processed(c, results + i))) return rc;
-      if (!assume) continue;
-      if (results[i].node >= 0 && (rc = assume_via_delta(c, qs[i], pools, results[i].node))) return rc;
-      if (results[i].node >= 0) drop_nominated(c, qs[i].uid);
-    }
-    c->last_diag = diag;
-    c->last_run_all = diag && c->run_all;
-    return KGPU_OK;
+  if ((rc = ensure(c, c->ticket, 9 * 64))) return rc;
+  HIP_OK(c, hipMemset(c->ticket.p, 0, 9 * 64));
+  return KGPU_OK;
+}
+
+// What every persistent batch launch (k_batch, k_cbatch, k_nbatch; synchronous or pipelined) sets the same
+// way, with the launch's counters and debug notes.  The granule layout stays with the issuer.  Returns
+// whether the launch is cooperative.
+bool fill_batch_args(kgpu_ctx* c, kgpu::BatchArgs& ba, int kidx, int groups, int per, int32_t first, int32_t cnt,
+                     int32_t assume, int64_t seq0, int32_t* abort, bool helper) {
+  ba.first = first;
+  ba.count = cnt;
+  ba.per = per;
+  ba.assume = assume;
+  ba.seq0 = seq0;
+  ba.abort = abort;
+  ba.abort_at = c->abort_at >= first && c->abort_at < first + cnt ? c->abort_at - first : -1;
+  const bool coop = c->coop || c->force_coop;
+  ba.hold = coop ? -1 : c->hold_group;
+  ++c->n_persist;
+  c->n_coop += coop ? 1 : 0;
+  note_geometry(c, 1, kidx, groups, per);
+  note_instantiation(c, kgpu::batch_row(c->spec), ba.R > 0, helper, cnt);
+  return coop;
+}
+
+// `ms` of device time for n pods; under KGPU_OPT_TIMING the kernels' own time and launch count as well
+void add_stats(const kgpu_ctx* c, kgpu_stats* stats, const kgpu_result* results, int32_t n, float ms, double kernel_ms,
+               int64_t launches) {
+  stats->pods += n;
+  stats->device_ms += ms;
+  int64_t placed = 0;
+  for (int32_t i = 0; i < n; ++i) placed += results[i].node >= 0;
+  stats->scheduled += placed;
+  if (c->timing) {
+    stats->eval_kernel_ms += kernel_ms;
+    stats->eval_launches += launches;
   }
-  if (!c->nom.list.empty()) {
-    if (c->comm)
-      return fail(c, KGPU_E_UNSUPPORTED, "nominated pods on a node-sharded engine (the two-pass filter runs unsharded)");
-    if (n > 1) {
-      // the nominator changes as pods are assumed: one cycle at a time
-      for (int32_t i = 0; i < n; ++i)
-        if ((rc = run_batch(c, qs + i, 1, pools, first_seq + i, results + i, stats, diag, assume))) return rc;
-      return KGPU_OK;
-    }
+}
+
+// Host records of an assumed pod for ForgetPod (and the pod table for later classes).  Each pointer is
+// null or addresses the query's own range: labels.count ints, scalars.count requests, ports.count ports.
+void record_assumed(kgpu_ctx* c, const kgpu_pod_query& q, int32_t node, const int32_t* pairs, const kgpu_scalar_req* sc,
+                    const kgpu_port* ports, const int32_t* own_tcls, int32_t n_own) {
+  kgpu_ctx::PodRow row;
+  row.node = node;
+  row.ns = q.ns;
+  row.flags = query_pod_flags(q);
+  if (pairs) row.pairs.assign(pairs, pairs + q.labels.count);
+  if (own_tcls) row.own_tcls.assign(own_tcls, own_tcls + n_own);
+  c->pod_rows.push_back(std::move(row));
+  kgpu_ctx::PodRec a;
+  a.node = node;  // global: the row lives on this shard or on another rank's
+  a.q = q;
+  a.active = true;
+  a.has_res = true;
+  if (sc) a.sc.assign(sc, sc + q.scalars.count);
+  if (ports) a.ports.assign(ports, ports + q.ports.count);
+  c->recs.push_back(std::move(a));
+}
+
+struct BatchCall {
+  const kgpu_pod_query* qs;
+  int32_t n;
+  const kgpu_pools* pools;
+  int64_t first_seq;
+  kgpu_result* results;
+  kgpu_stats* stats;
+  bool diag;
+  int32_t assume;
+};
+
+// A node listed twice: the device assume updates one row only, so place pods one at a time
+// and apply NodeInfo.AddPod to every row of the chosen node through k_delta.  Every call takes this
+// loop, with or without assume: alias_processed corrects each cycle's count.
+int alias_cycles(kgpu_ctx* c, const BatchCall& a) {
+  struct Nested {
+    kgpu_ctx* c;
+    ~Nested() { c->in_alias = false; }
+  } nested{c};
+  c->in_alias = true;
+  int rc;
+  // Each cycle runs on the per-pod launches (diag), which leave every row's status word behind:
+  // alias_processed needs them.
+  for (int32_t i = 0; i < a.n; ++i) {
+    if ((rc = run_batch(c, a.qs + i, 1, a.pools, a.first_seq + i, a.results + i, a.stats, true, 0))) return rc;
+    if ((rc = alias_processed(c, a.results + i))) return rc;
+    if (!a.assume) continue;
+    if (a.results[i].node >= 0 && (rc = assume_via_delta(c, a.qs[i], a.pools, a.results[i].node))) return rc;
+    if (a.results[i].node >= 0) drop_nominated(c, a.qs[i].uid);
   }
-  // A short cycle (kgpu_schedule_one, small batches) moves what it sends -- DevState, queries and the
-  // items of its arena -- with ONE copy from pinned memory into one device block, and its kernels
-  // write the result records straight into pinned host memory: every stream operation saved is
-  // several microseconds of the per-cycle latency.
-  const bool short_cycle = n <= kShortCycle;
-  ArenaScope arena_scope{c};
-  if (short_cycle) {
-    if (!c->cyc_host) HIP_OK(c, hipHostMalloc(&c->cyc_host, kCycHostBytes, hipHostMallocDefault));
-    if ((rc = ensure(c, c->dstate, kCycHostBytes))) return rc;
-    if (!c->res_pin) {
-      HIP_OK(c, hipHostMalloc(&c->res_pin, kCycResBytes + 64, hipHostMallocCoherent | hipHostMallocMapped));
-      void* d = nullptr;
-      HIP_OK(c, hipHostGetDevicePointer(&d, c->res_pin, 0));
-      c->res_dev = static_cast<kgpu_result*>(d);
-    }
-    // the previous cycle's arena copy may still read cyc_host when that cycle failed before its
-    // stream synchronize
-    if (c->ar.inflight) SYNC_OK(c);
-    const size_t first = (kDsQueryOff + sizeof(kgpu_pod_query) * (size_t)n + 255) & ~(size_t)255;
-    c->ar.begin(first, c->ar_limit > 0 ? std::min(kCycHostBytes, first + c->ar_limit) : 0);
-    // every record the kernels write overwrites this: the host trace's "record landed" step, and the
-    // second half of a one-pod cycle's completion (its word and its record)
-    for (int32_t i = 0; i < n; ++i)
-      __atomic_store_n(&static_cast<kgpu_result*>(c->res_pin)[i].evaluated, INT32_MIN, __ATOMIC_RELAXED);
-  }
-  c->tb_abort_mapped = false;
-  ht(c, 0);
-  Staged sg;
-  if ((rc = stage_topology(c, qs, n, pools, sg))) return rc;
-  ht(c, 1);  // 1: topology staging (QPlan, classes)
-  std::vector<kgpu::QPlan>& plans = sg.plans;
-  std::vector<int32_t>& aux = sg.aux;
-  std::vector<kgpu::TTerm>& aux_terms = sg.aux_terms;
-  const bool topo_on = sg.topo_on;
+  c->last_diag = a.diag;
+  c->last_run_all = a.diag && c->run_all;
+  return KGPU_OK;
+}
+
+// the nominator changes as pods are assumed: one cycle at a time
+int nominated_cycles(kgpu_ctx* c, const BatchCall& a) {
+  int rc;
+  for (int32_t i = 0; i < a.n; ++i)
+    if ((rc = run_batch(c, a.qs + i, 1, a.pools, a.first_seq + i, a.results + i, a.stats, a.diag, a.assume))) return rc;
+  return KGPU_OK;
+}
+
+// Everything one issue of a call shares between its stages.
+struct Cycle : BatchCall {
+  kgpu_ctx* c;
+  kgpu_route::CycleFacts facts;
+  kgpu_route::CycleRoute r;
+  Staged sg;  // topology plans
+  std::vector<PodKind> kinds;
   int64_t batch_ports = 0;
-  if (assume)
-    for (int32_t i = 0; i < n; ++i) batch_ports += qs[i].ports.count;
-  if ((rc = reserve_ports(c, batch_ports))) return rc;
-  // the cycles whose only kernel is k_eval (inline_q below): their pools may stay in pinned memory
-  const bool zc = short_cycle && n == 1 && diag && !topo_on && c->comm == nullptr && !(c->xg_nranks > 1) &&
-                  c->st.cut_state == nullptr && c->nom.list.empty() && !c->timing && !c->phase_trace;
-  if ((rc = upload_pools(c, pools, zc))) return rc;
+  PreemptStage nps;  // nominated pods that apply to this pod: pass 1 runs in k_victims before the filter phase
+  const kgpu::PreemptArgs* nom_dev = nullptr;
+  DevState st;  // the image the kernels read
+  const DevState* dst = nullptr;
+  int blocks = 0;
+  // persistent geometries: one workgroup per CU at most, K node rows per lane (in registers up to K = 4,
+  // streamed from the node columns at K = 8)
+  int kidx = -1, per = 0, groups = 0;
+  int tgeo = -1, tper = 0, tgroups = 0;
+  bool timed = false;  // the cycle's device time is reported in stats only
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  size_t ev = 2;  // event cursor of KGPU_OPT_TIMING's per-launch pairs
+  int64_t timed_passes = 0;
+  bool used_persistent = false;
+  int64_t cut_pods = 0;       // this call's pods inside cut-mode runs (taken back when the call is issued again)
+  int64_t cut_topo_pods = 0;  // ... and inside cut-mode persistent topology runs
+  int64_t cut_topo_one = 0;   // ... and inside one-pod cut-mode topology runs (diagnostic cycles)
+  int64_t norm_pods = 0;      // ... and inside normalize-pass persistent runs (k_nbatch)
+  int32_t* abort_word = nullptr;  // one for every persistent run of this batch (OR-ed on the device)
+  int32_t* done_word = nullptr;   // the pinned completion word of the call's last kernel (one-pod cycles)
+  bool diag_zeroed = false;
+  int32_t scratch_zeroed_for = -1;
+  int32_t port_overflow = 0;
+  kgpu_result* res_host = nullptr;
+  std::deque<std::array<void*, 2>> run_ptrs;  // kept until the stream is synchronized
+  std::deque<TRun> runs;                       // (async copies read its vectors)
+  Cycle(kgpu_ctx* ctx, const BatchCall& a) : BatchCall(a), c(ctx) {}
+};
+
+// A short cycle (kgpu_schedule_one, small batches) moves what it sends -- DevState, queries and the
+// items of its arena -- with ONE copy from pinned memory into one device block, and its kernels
+// write the result records straight into pinned host memory: every stream operation saved is
+// several microseconds of the per-cycle latency.
+int begin_short_cycle(kgpu_ctx* c, int32_t n) {
+  int rc;
+  if (!c->cyc_host) HIP_OK(c, hipHostMalloc(&c->cyc_host, kCycHostBytes, hipHostMallocDefault));
+  if ((rc = ensure(c, c->dstate, kCycHostBytes))) return rc;
+  if (!c->res_pin) {
+    HIP_OK(c, hipHostMalloc(&c->res_pin, kCycResBytes + 64, hipHostMallocCoherent | hipHostMallocMapped));
+    void* d = nullptr;
+    HIP_OK(c, hipHostGetDevicePointer(&d, c->res_pin, 0));
+    c->res_dev = static_cast<kgpu_result*>(d);
+  }
+  // the previous cycle's arena copy may still read cyc_host when that cycle failed before its
+  // stream synchronize
+  if (c->ar.inflight) SYNC_OK(c);
+  const size_t first = (kDsQueryOff + sizeof(kgpu_pod_query) * (size_t)n + 255) & ~(size_t)255;
+  c->ar.begin(first, c->ar_limit > 0 ? std::min(kCycHostBytes, first + c->ar_limit) : 0);
+  // every record the kernels write overwrites this: the host trace's "record landed" step, and the
+  // second half of a one-pod cycle's completion (its word and its record)
+  for (int32_t i = 0; i < n; ++i)
+    __atomic_store_n(&static_cast<kgpu_result*>(c->res_pin)[i].evaluated, INT32_MIN, __ATOMIC_RELAXED);
+  return KGPU_OK;
+}
+
+kgpu_route::CycleFacts cycle_facts(const kgpu_ctx* c, const BatchCall& a, bool topo_on) {
+  kgpu_route::CycleFacts f;
+  f.n = a.n;
+  f.short_max = kShortCycle;
+  f.diag = a.diag;
+  f.run_all = a.diag && c->run_all;
+  f.in_alias = c->in_alias;
+  f.topo_on = topo_on;
+  f.has_comm = c->comm != nullptr;
+  f.multi_rank = c->xg_nranks > 1;
+  f.xgmi = c->xgmi;
+  f.cut_state = c->st.cut_state != nullptr;
+  f.nom_listed = !c->nom.list.empty();
+  f.timing = c->timing;
+  f.phase_trace = c->phase_trace;
+  f.arena_on = c->ar.on;
+  f.persistent = c->persistent;
+  f.cut_persistent = c->cut_persistent;
+  f.tfast = c->tfast;
+  f.cut_topo_persistent = c->cut_topo_persistent;
+  f.cut_topo_one = c->cut_topo_one;
+  f.nbatch_row_ok = kgpu::nbatch_row_ok(c->spec);
+  // the raw taint maximum, at most 64 per taint word, must fit the statistics granule's field
+  f.taint_fits = 64 * (int64_t)std::max(c->st.TW, 0) < ((int64_t)1 << kgpu::kNormTaintBits);
+  f.norm_persistent = c->norm_persistent;
+  f.K = c->st.K;
+  return f;
+}
+
+// Topology plans, ports, pools, then DevState and the queries: through the arena (short cycles: the
+// arena copy moves them) or the pinned batch block.
+int stage_cycle(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  const int32_t n = cy.n;
+  int rc;
+  if ((rc = stage_topology(c, cy.qs, n, cy.pools, cy.sg))) return rc;
+  ht(c, 1);  // 1: topology staging (QPlan, classes)
+  cy.facts = cycle_facts(c, cy, cy.sg.topo_on);
+  cy.r = kgpu_route::gates_call(cy.facts);
+  const bool short_cycle = cy.r.short_cycle;
+  if (cy.assume)
+    for (int32_t i = 0; i < n; ++i) cy.batch_ports += cy.qs[i].ports.count;
+  if ((rc = reserve_ports(c, cy.batch_ports))) return rc;
+  if ((rc = upload_pools(c, cy.pools, cy.r.zc))) return rc;
   ht(c, 2);  // 2: ports, pools
   if (!short_cycle) {
     if ((rc = ensure(c, c->queries, sizeof(kgpu_pod_query) * (size_t)n))) return rc;
-    if ((rc = stage_h2d(c, c->queries.p, qs, sizeof(kgpu_pod_query) * (size_t)n))) return rc;
+    if ((rc = stage_h2d(c, c->queries.p, cy.qs, sizeof(kgpu_pod_query) * (size_t)n))) return rc;
     if ((rc = ensure(c, c->results, sizeof(kgpu_result) * (size_t)n))) return rc;
   }
-  if (!c->ticket.p) {  // resolve_tail's counters: the top one and 8 group counters, a 64-byte line each
-    if ((rc = ensure(c, c->ticket, 9 * 64))) return rc;
-    HIP_OK(c, hipMemset(c->ticket.p, 0, 9 * 64));
-  }
-  DevState st = c->st;
+  if ((rc = ensure_ticket(c))) return rc;
+  DevState& st = cy.st;
+  st = c->st;
   st.ticket = static_cast<int32_t*>(c->ticket.p);
   // runAllFilters: a diagnostic cycle's statuses merge every failing plugin (k_eval's runtime profile,
   // k_topo_filter, k_victims' nominated pass); placements do not depend on it
-  st.run_all = (diag && c->run_all) ? 1 : 0;
+  st.run_all = cy.facts.run_all ? 1 : 0;
   st.queries = short_cycle ? reinterpret_cast<const kgpu_pod_query*>(static_cast<char*>(c->dstate.p) + kDsQueryOff)
                            : static_cast<const kgpu_pod_query*>(c->queries.p);
   // a short cycle's records go straight to pinned host memory (no read-back copy)
   st.results = short_cycle ? c->res_dev : static_cast<kgpu_result*>(c->results.p);
   // Per-plugin scores of a diagnostic cycle: every pod of a batch without topology pods goes
-  // through k_eval, which then zeroes each node's rows itself; a one-pod persistent topology run's
-  // k_tbatch does too; otherwise one memset does, issued before the first launch that needs it.
-  const bool zero_diag = diag && !topo_on && c->comm == nullptr;
-  bool diag_zeroed = !diag || zero_diag;
-  if (!diag) {
+  // through k_eval, which then zeroes each node's rows itself (zero_diag); a one-pod persistent topology
+  // run's k_tbatch does too; otherwise one memset does, issued before the first launch that needs it.
+  cy.diag_zeroed = !cy.diag || cy.r.zero_diag;
+  if (!cy.diag) {
     st.diag_raw = nullptr;
     st.diag_norm = nullptr;
   }
-  auto zero_diag_rows = [&]() -> int {
-    if (!diag_zeroed) {
-      HIP_OK(c, hipMemsetAsync(c->st.diag_raw, 0, sizeof(int64_t) * 2 * KGPU_NUM_SCORES * (size_t)c->st.N, c->stream));
-      diag_zeroed = true;
-    }
-    return KGPU_OK;
-  };
-  // nominated pods that apply to this pod: pass 1 runs in k_victims before the filter phase
-  PreemptStage nps;
-  const kgpu::PreemptArgs* nom_dev = nullptr;
   if (!c->nom.list.empty()) {
-    stage_nominated(c, qs[0], pools, topo_on ? &plans[0] : nullptr, nps.n_off, nps.neff, nps.aux);
-    if (!nps.neff.empty()) {
-      if ((rc = upload_preempt(c, nps, nullptr, 0, 0, nullptr, &nom_dev))) return rc;
+    stage_nominated(c, cy.qs[0], cy.pools, cy.sg.topo_on ? &cy.sg.plans[0] : nullptr, cy.nps.n_off, cy.nps.neff, cy.nps.aux);
+    if (!cy.nps.neff.empty()) {
+      if ((rc = upload_preempt(c, cy.nps, nullptr, 0, 0, nullptr, &cy.nom_dev))) return rc;
       st.nom_status = c->pa_host.nom_status;
     }
   }
+  kgpu_route::gates_nominated(cy.r, cy.facts, cy.nom_dev != nullptr);
   if ((rc = ensure(c, c->dstate, sizeof(DevState)))) return rc;
   c->st_batch = st;
-  // A one-pod diagnostic cycle on k_eval + k_final (kgpu_schedule_one) passes its query in the
-  // launch arguments; its DevState is re-sent only when it differs from the image already there.
-  const bool inline_q = short_cycle && n == 1 && diag && !topo_on && c->comm == nullptr && !(c->xg_nranks > 1) &&
-                        c->st.cut_state == nullptr && nom_dev == nullptr;
   if (short_cycle) {
+    // A one-pod diagnostic cycle on k_eval + k_final (kgpu_schedule_one) passes its query in the
+    // launch arguments (inline_q); its DevState is re-sent only when it differs from the image already there.
     char* h = static_cast<char*>(c->cyc_host);
     const bool ds_same = c->ds_ptr == c->dstate.p && std::memcmp(&c->ds_last, &c->st_batch, sizeof(DevState)) == 0;
-    // staged only: the arena copy (arena_flush, below or in run_tbatch) moves it
-    if (!inline_q) {
+    // staged only: the arena copy (arena_flush, in run_batch_once or in run_tbatch) moves it
+    if (!cy.r.inline_q) {
       std::memcpy(h, &c->st_batch, sizeof(DevState));
-      std::memcpy(h + kDsQueryOff, qs, sizeof(kgpu_pod_query) * (size_t)n);
+      std::memcpy(h + kDsQueryOff, cy.qs, sizeof(kgpu_pod_query) * (size_t)n);
       c->ar.mark(0, kDsQueryOff + sizeof(kgpu_pod_query) * (size_t)n);
     } else if (!ds_same) {
       std::memcpy(h, &c->st_batch, sizeof(DevState));
@@ -2303,458 +2436,456 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     if ((rc = stage_h2d(c, c->dstate.p, &c->st_batch, sizeof(DevState)))) return rc;
     ht(c, 3);  // 3: queries and DevState copies (API calls)
   }
-  const DevState* dst = static_cast<const DevState*>(c->dstate.p);
-  const int blocks = kgpu::eval_blocks(st.N);
-  hipEvent_t t0 = get_event(c, 0), t1 = get_event(c, 1);
-  const bool timed = stats != nullptr || c->timing;  // the cycle's device time is reported in stats only
-  if (timed) HIP_OK(c, hipEventRecord(t0, c->stream));
-  size_t ev = 2;
-  int64_t timed_passes = 0;
-  // Persistent geometry: one workgroup per CU at most, K node rows per lane (in registers up to K = 4,
-  // streamed from the node columns at K = 8).
-  int per = 0, groups = 0;
-  const bool xg = c->xg_nranks > 1 && c->xgmi;  // persistent runs exchange granules over xGMI
-  const bool sharded = c->comm != nullptr || xg;
-  const bool cut = c->st.cut_state != nullptr;  // percentageOfNodesToScore trims the feasible set
-  if (cut && sharded)
+  return KGPU_OK;
+}
+
+// The call's routes: geometries, the pods' kinds, the abort word.
+int plan_routes(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  kgpu_route::CycleRoute& r = cy.r;
+  const int32_t n = cy.n;
+  int rc;
+  cy.dst = static_cast<const DevState*>(c->dstate.p);
+  cy.blocks = kgpu::eval_blocks(cy.st.N);
+  cy.t0 = get_event(c, 0);
+  cy.t1 = get_event(c, 1);
+  cy.timed = cy.stats != nullptr || c->timing;
+  if (cy.timed) HIP_OK(c, hipEventRecord(cy.t0, c->stream));
+  if (r.cut && r.sharded)
     return fail(c, KGPU_E_UNSUPPORTED, "percentageOfNodesToScore < 100 on a node-sharded engine (nextStartNodeIndex "
                                        "rotates over the whole cluster): use 100 when sharding");
-  int kidx = -1;
-  if (c->persistent && !diag && (!cut || c->cut_persistent) && !nom_dev) {
-    if (xg) {
-      kidx = c->xg_geo;
-      per = c->xg_per;
-      groups = c->xg_groups;
-    } else if (!sharded) {
-      kidx = kgpu::batch_geometry(st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
-                                  &per, &groups, c->batch_geo_first);
-    }
+  if (r.batch && r.xg) {
+    cy.kidx = c->xg_geo;
+    cy.per = c->xg_per;
+    cy.groups = c->xg_groups;
+  } else if (r.batch) {
+    cy.kidx = kgpu::batch_geometry(cy.st.N, persistent_groups(c), &cy.per, &cy.groups, c->batch_geo_first);
   }
-  std::deque<std::array<void*, 2>> run_ptrs;  // kept until the stream is synchronized
-  if (kidx >= 0 && !xg && (rc = ensure(c, c->batch_ptrs, sizeof(void*) * 2 * (size_t)(n + 1)))) return rc;
-  std::vector<uint8_t> norm((size_t)n), topo((size_t)n, 0);
-  // pods that need the normalize pass or whose scoring fails take the one-launch-per-pod path;
-  // pods with topology state take the topology pipeline
-  for (int32_t i = 0; i < n; ++i) {
-    norm[(size_t)i] = (diag || needs_norm(c, qs[i], pools) || (qs[i].flags & KGPU_Q_SCORE_ERROR)) ? 1 : 0;
-    if (topo_on) topo[(size_t)i] = plans[(size_t)i].topo ? 1 : 0;
-  }
-  // Sharded: after the evaluation (and normalize) of pod k, pack this shard's record and
-  // all-gather it on the same stream; the next launch resolves pod k over every rank's record.
-  auto exchange = [&](int parity, int what) -> int {
-    if (!c->comm)
-      return fail(c, KGPU_E_STATE, "this pod needs the per-pod RCCL exchange: call kgpu_comm_init (xGMI mailboxes "
-                                   "carry persistent runs only)");
-    if (kgpu::launch_shard_pack(dst, parity, blocks, what, c->stream))
-      return fail(c, KGPU_E_DEVICE, "k_shard_pack launch failed");
-    const ncclResult_t r =
-        what == 0 ? rccl().AllGather(c->st.shard_send_key, c->st.shard_keys + (size_t)parity * kgpu::kMaxRanks,
-                                  sizeof(BlkKey) / 8, ncclUint64, c->comm, c->stream)
-                  : rccl().AllGather(c->st.shard_send_stat, c->st.shard_stats + (size_t)parity * kgpu::kMaxRanks,
-                                  sizeof(BlkStat) / 4, ncclInt32, c->comm, c->stream);
-    if (r != ncclSuccess) return fail(c, KGPU_E_DEVICE, std::string("ncclAllGather: ") + rccl().GetErrorString(r));
-    return KGPU_OK;
-  };
-  bool used_persistent = false;
-  int64_t cut_pods = 0;  // this call's pods inside cut-mode runs (taken back when the call is issued again)
-  int64_t cut_topo_pods = 0;  // ... and inside cut-mode persistent topology runs
-  int64_t cut_topo_one = 0;   // ... and inside one-pod cut-mode topology runs (diagnostic cycles)
-  int64_t norm_pods = 0;      // ... and inside normalize-pass persistent runs (k_nbatch)
-  // KGPU_OPT_NORM_PERSISTENT: pods that need the normalize pass and carry no topology state go through
-  // k_nbatch (unsharded batch runs; the profile row must hold a normalized plugin and the raw taint maximum,
-  // at most 64 per taint word, must fit the statistics granule's field)
-  std::vector<uint8_t> nrm;
-  if (c->norm_persistent > 0 && kidx >= 0 && !sharded && !diag && !nom_dev && kgpu::nbatch_row_ok(c->spec) &&
-      64 * (int64_t)std::max(st.TW, 0) < ((int64_t)1 << kgpu::kNormTaintBits)) {
-    nrm.assign((size_t)n, 0);
-    for (int32_t k = 0; k < n; ++k)
-      nrm[(size_t)k] = (!(qs[k].flags & KGPU_Q_SCORE_ERROR) && !topo[(size_t)k] && needs_norm(c, qs[k], pools)) ? 1 : 0;
-  }
-  int32_t* done_word = nullptr;  // the pinned completion word of the call's last kernel (one-pod cycles)
-  // one abort word for every persistent run of this batch (OR-ed on the device)
-  int rc_abort = ensure(c, c->abort_buf, 64);
-  if (rc_abort) return rc_abort;
-  int32_t* abort_word = static_cast<int32_t*>(c->abort_buf.p);
-  int tper = 0, tgroups = 0;
-  // node-sharded engines take the persistent topology kernel over the xGMI mailboxes (the XG
-  // instantiation); without them, the per-pod RCCL pipeline
-  // a diagnostic cycle (kgpu_schedule_one: status words and per-plugin scores) of one topology pod
-  // runs as a one-pod persistent run too
-  // under a cut (percentageOfNodesToScore < 100) batch runs take its cut-mode instantiation
-  // (KGPU_OPT_CUT_TOPO_PERSISTENT); diagnostic cycles keep the per-pod pipeline (k_cut) unless
-  // KGPU_OPT_CUT_TOPO_ONE sends them through a one-pod cut-mode run (not the aliased-list loop's cycles)
-  const int tgeo = (topo_on && c->tfast && (!diag || (n == 1 && !st.run_all)) && (!sharded || xg) &&
-                    (!cut || (c->cut_topo_persistent && (!diag || (c->cut_topo_one && !c->in_alias)))) && !nom_dev &&
-                    st.K <= 64)
-                       ? kgpu::tbatch_geometry(st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
-                                               &tper, &tgroups, c->tbatch_geo_first)
-                       : -1;
+  r.batch = cy.kidx >= 0;
+  r.nbatch = r.nbatch && r.batch;
+  if (r.batch && !r.xg && (rc = ensure(c, c->batch_ptrs, sizeof(void*) * 2 * (size_t)(n + 1)))) return rc;
+  cy.kinds.resize((size_t)n);
+  for (int32_t i = 0; i < n; ++i)
+    cy.kinds[(size_t)i] = kgpu_route::pod_kind(cy.sg.topo_on && cy.sg.plans[(size_t)i].topo,
+                                               (cy.qs[i].flags & KGPU_Q_SCORE_ERROR) != 0, needs_norm(c, cy.qs[i], cy.pools));
+  if ((rc = ensure(c, c->abort_buf, 64))) return rc;
+  cy.abort_word = static_cast<int32_t*>(c->abort_buf.p);
+  if (r.tbatch) cy.tgeo = kgpu::tbatch_geometry(cy.st.N, persistent_groups(c), &cy.tper, &cy.tgroups, c->tbatch_geo_first);
+  r.tbatch = cy.tgeo >= 0;
   // A one-pod persistent topology run (kgpu_schedule_one of a topology pod) keeps its abort word in
   // the arena, and k_tbatch copies it into res_pin at exit: no memset, no read-back copy.
-  const bool tb_arena = short_cycle && n == 1 && topo[0] && tgeo >= 0 && !xg && c->ar.on;
+  r.tb_arena = r.short_cycle && n == 1 && cy.kinds[0] == PodKind::kTopo && r.tbatch && !r.xg && cy.facts.arena_on;
+  kgpu_route::set_run_limits(r, cy.groups, kgpu::kXgmiRing / 2);
   // zeroed only when a persistent run can start (a one-launch-per-pod cycle never reads it)
-  if (kidx >= 0 || (tgeo >= 0 && !tb_arena)) HIP_OK(c, hipMemsetAsync(c->abort_buf.p, 0, 64, c->stream));
-  std::deque<TRun> runs;
-  int32_t scratch_zeroed_for = -1;
-  int32_t i = 0;
-  while (i < n) {
-    int32_t j = i;
-    if (topo[(size_t)i] && tgeo >= 0) {
-      runs.emplace_back();  // kept until the stream is synchronized (async copies read its vectors)
-      TRun& tr = runs.back();
-      kgpu_pools empty{};
-      const kgpu_pools* pp = pools ? pools : &empty;
-      ht(c, 3);  // 3: DevState / queries staged, geometry
-      while (j < n && topo[(size_t)j] && t_add(tr, c, qs[j], plans[(size_t)j], pp, aux, aux_terms, j)) ++j;
-      ht(c, 4);  // 4: the run's tables planned (t_add)
-      if (j > i) {
-        if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
-        if ((rc = run_tbatch(c, tr, i, j - i, first_seq, assume, tper, tgroups, tgeo, tb_arena ? nullptr : abort_word, xg,
-                             diag, cut)))
-          return rc;
-        if (cut) (diag ? cut_topo_one : cut_topo_pods) += j - i;
-        // the one-pod run's last workgroup copies the abort word into pinned memory after everything is
-        // written back: the call's completion word
-        done_word = (c->tb_abort_mapped && !c->timing && !c->phase_trace)
-                        ? reinterpret_cast<int32_t*>(static_cast<char*>(c->res_pin) + kCycAbortOff)
-                        : nullptr;
-        if (diag) diag_zeroed = true;  // k_tbatch zeroed the rows (a diagnostic run is one pod)
-        if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-        ev += 2;
-        timed_passes += j - i;
-        used_persistent = true;
-        i = j;
-        continue;
-      }
+  if (r.batch || (r.tbatch && !r.tb_arena)) HIP_OK(c, hipMemsetAsync(c->abort_buf.p, 0, 64, c->stream));
+  return KGPU_OK;
+}
+
+int zero_diag_rows(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  if (!cy.diag_zeroed) {
+    HIP_OK(c, hipMemsetAsync(c->st.diag_raw, 0, sizeof(int64_t) * 2 * KGPU_NUM_SCORES * (size_t)c->st.N, c->stream));
+    cy.diag_zeroed = true;
+  }
+  return KGPU_OK;
+}
+
+// KGPU_OPT_TIMING: every launch (or run) sits between a pair of events
+int timing_mark(Cycle& cy, size_t k) {
+  if (cy.c->timing) HIP_OK(cy.c, hipEventRecord(get_event(cy.c, cy.ev + k), cy.c->stream));
+  return KGPU_OK;
+}
+int timing_close(Cycle& cy, int64_t passes) {
+  int rc = timing_mark(cy, 1);
+  cy.ev += 2;
+  cy.timed_passes += passes;
+  return rc;
+}
+
+// Sharded: after the evaluation (and normalize) of pod k, pack this shard's record and
+// all-gather it on the same stream; the next launch resolves pod k over every rank's record.
+int exchange(Cycle& cy, int parity, int what) {
+  kgpu_ctx* c = cy.c;
+  if (!c->comm)
+    return fail(c, KGPU_E_STATE, "this pod needs the per-pod RCCL exchange: call kgpu_comm_init (xGMI mailboxes "
+                                 "carry persistent runs only)");
+  if (kgpu::launch_shard_pack(cy.dst, parity, cy.blocks, what, c->stream))
+    return fail(c, KGPU_E_DEVICE, "k_shard_pack launch failed");
+  const ncclResult_t r =
+      what == 0 ? rccl().AllGather(c->st.shard_send_key, c->st.shard_keys + (size_t)parity * kgpu::kMaxRanks,
+                                sizeof(BlkKey) / 8, ncclUint64, c->comm, c->stream)
+                : rccl().AllGather(c->st.shard_send_stat, c->st.shard_stats + (size_t)parity * kgpu::kMaxRanks,
+                                sizeof(BlkStat) / 4, ncclInt32, c->comm, c->stream);
+  if (r != ncclSuccess) return fail(c, KGPU_E_DEVICE, std::string("ncclAllGather: ") + rccl().GetErrorString(r));
+  return KGPU_OK;
+}
+
+// A persistent topology run (k_tbatch) from pod i over the topology pods t_add accepts; *end == i when it
+// refuses the first (nothing was issued: the pod takes the topology pipeline).
+int issue_tbatch_run(Cycle& cy, int32_t i, int32_t* end) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  int32_t j = i;
+  cy.runs.emplace_back();  // kept until the stream is synchronized (async copies read its vectors)
+  TRun& tr = cy.runs.back();
+  kgpu_pools empty{};
+  const kgpu_pools* pp = cy.pools ? cy.pools : &empty;
+  ht(c, 3);  // 3: DevState / queries staged, geometry
+  while (j < cy.n && cy.kinds[(size_t)j] == PodKind::kTopo &&
+         t_add(tr, c, cy.qs[j], cy.sg.plans[(size_t)j], pp, cy.sg.aux, cy.sg.aux_terms, j))
+    ++j;
+  ht(c, 4);  // 4: the run's tables planned (t_add)
+  *end = j;
+  if (j == i) return KGPU_OK;
+  if ((rc = timing_mark(cy, 0))) return rc;
+  if ((rc = run_tbatch(c, tr, i, j - i, cy.first_seq, cy.assume, cy.tper, cy.tgroups, cy.tgeo,
+                       cy.r.tb_arena ? nullptr : cy.abort_word, cy.r.xg, cy.diag, cy.r.cut)))
+    return rc;
+  if (cy.r.cut) (cy.diag ? cy.cut_topo_one : cy.cut_topo_pods) += j - i;
+  // the one-pod run's last workgroup copies the abort word into pinned memory after everything is
+  // written back: the call's completion word
+  cy.done_word = (c->tb_abort_mapped && !c->timing && !c->phase_trace)
+                     ? reinterpret_cast<int32_t*>(static_cast<char*>(c->res_pin) + kCycAbortOff)
+                     : nullptr;
+  if (cy.diag) cy.diag_zeroed = true;  // k_tbatch zeroed the rows (a diagnostic run is one pod)
+  cy.used_persistent = true;
+  return timing_close(cy, j - i);
+}
+
+// Node-sharded topology pod: every rank builds the histograms of
+// its shard; RCCL sums them (and ORs / mins / maxes the header) between the phases, so
+// every rank filters and scores against the cluster-wide TpPairToMatchNum, topology
+// scores, sizes and normalize extremes; the winner exchange is the non-topology one.
+int issue_topo_pod_sharded(Cycle& cy, const PodArgs& a, const kgpu::QPlan& pl, int64_t min_values, int64_t next) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  if (!c->comm) return fail(c, KGPU_E_STATE, "topology pods on a sharded engine need kgpu_comm_init");
+  int64_t* sc = c->st.scratch;
+  auto ar = [&](void* buf, size_t cnt, ncclDataType_t t, ncclRedOp_t op) -> int {
+    if (!cnt) return KGPU_OK;
+    const ncclResult_t r = rccl().AllReduce(buf, buf, cnt, t, op, c->comm, c->stream);
+    return r == ncclSuccess ? KGPU_OK : fail(c, KGPU_E_DEVICE, std::string("ncclAllReduce: ") + rccl().GetErrorString(r));
+  };
+  auto phase = [&](int ph, int64_t extra) -> int {
+    return kgpu::launch_topo_phase(cy.dst, a, ph, cy.blocks, extra, c->stream) ? fail(c, KGPU_E_DEVICE, "topology phase launch failed")
+                                                                               : KGPU_OK;
+  };
+  if ((rc = phase(0, 0)) || (rc = ar(sc, (size_t)pl.scratch_len, ncclInt64, ncclSum))) return rc;
+  if (min_values > 0 && (rc = phase(1, min_values))) return rc;
+  if ((rc = phase(2, 0))) return rc;
+  bool soft_sizes = false;
+  for (int k = 0; k < pl.n_soft; ++k) {
+    const kgpu::TSpread& t = pl.soft[k];
+    if (t.is_hostname || t.key < 0) continue;
+    if ((rc = ar(sc + pl.slot_off[t.rslot], (size_t)std::max(c->key_n_values[(size_t)t.key], 1), ncclInt64, ncclSum)))
+      return rc;
+    soft_sizes |= t.first_of_key != 0;
+  }
+  int32_t* h32 = reinterpret_cast<int32_t*>(sc);
+  const size_t i_feas = offsetof(kgpu::TopoHdr, feas_nonign) / 4, i_zones = offsetof(kgpu::TopoHdr, have_zones) / 4;
+  if (pl.n_soft && (rc = ar(h32 + i_feas, 1, ncclInt32, ncclSum))) return rc;
+  if (soft_sizes && (rc = phase(3, 0))) return rc;
+  if ((rc = phase(4, 0))) return rc;
+  // score extremes are max-encoded words (pts_min .. dpts_max), zone sums add, have_zones ORs
+  if ((rc = ar(sc + offsetof(kgpu::TopoHdr, pts_min) / 8, 5, ncclUint64, ncclMax)) ||
+      (rc = ar(h32 + i_zones, 1, ncclInt32, ncclMax)) ||
+      (rc = ar(sc + kgpu::kHdrWords, (size_t)std::max(c->st.n_zones, 0), ncclInt64, ncclSum)) ||
+      (rc = exchange(cy, a.parity, 1)) || (rc = phase(5, cy.blocks)) || (rc = exchange(cy, a.parity, 0)) ||
+      (rc = phase(6, next)))
+    return rc;
+  return KGPU_OK;
+}
+
+// The per-pod topology pipeline: pod i alone.
+int issue_topo_pod(Cycle& cy, int32_t i) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  ++c->state_launches;
+  if ((rc = zero_diag_rows(cy))) return rc;
+  const kgpu::QPlan& pl = cy.sg.plans[(size_t)i];
+  // the previous pod's resolve launch zeroes this pod's scratch only when it went through this
+  // pipeline too (a persistent topology run in between leaves it dirty)
+  if (cy.scratch_zeroed_for != i)
+    HIP_OK(c, hipMemsetAsync(c->st.scratch, 0, sizeof(int64_t) * (size_t)pl.scratch_len, c->stream));
+  int64_t min_values = 0;
+  for (int k = 0; k < pl.n_hard; ++k)
+    if (pl.hard[k].key >= 0) min_values = std::max<int64_t>(min_values, c->key_n_values[pl.hard[k].key]);
+  const int64_t next =
+      (i + 1 < cy.n && cy.kinds[(size_t)i + 1] == PodKind::kTopo) ? cy.sg.plans[(size_t)i + 1].scratch_len : 0;
+  PodArgs a{};
+  a.pod = i;
+  a.prev = -1;
+  a.parity = i & 1;
+  a.norm = 1;
+  a.assume = cy.assume;
+  a.diag = cy.diag ? 1 : 0;
+  a.cut = cy.r.cut ? 1 : 0;
+  a.seq = cy.first_seq + i;
+  if ((rc = timing_mark(cy, 0))) return rc;
+  if (cy.r.sharded) {
+    if ((rc = issue_topo_pod_sharded(cy, a, pl, min_values, next))) return rc;
+  } else {
+    if (c->topo_fused && !c->gbar.p) {
+      if ((rc = ensure(c, c->gbar, 64))) return rc;
+      HIP_OK(c, hipMemsetAsync(c->gbar.p, 0, 64, c->stream));
+      c->bar_base = 0;
+    }
+    if (kgpu::launch_topo(cy.dst, a, cy.blocks, min_values, next, c->topo_fused,
+                          static_cast<unsigned long long*>(c->gbar.p), c->bar_base, c->cfg.n_filters, c->stream,
+                          cy.nom_dev, cy.st.N))
+      return fail(c, KGPU_E_DEVICE, "topology pipeline launch failed");
+    if (c->topo_fused && !cy.r.cut && !cy.nom_dev)
+      c->bar_base += (unsigned long long)kgpu::topo_barriers(min_values) * (unsigned long long)cy.blocks;
+  }
+  cy.scratch_zeroed_for = next > 0 ? i + 1 : -1;
+  return timing_close(cy, 1);
+}
+
+// Pods [i, j) in one persistent launch of k_nbatch: the run starts at a normalize-pass pod
+// (kgpu_route::segment_end has the rule for what it absorbs).
+int issue_nbatch_run(Cycle& cy, int32_t i, int32_t j) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  const int32_t cnt = j - i;
+  const int groups = cy.groups;
+  const size_t rounds = cy.r.cut ? 3 : 2;
+  kgpu::BatchArgs ba{};
+  // layout: granules [cnt][rounds][groups] u64 | position words [cnt] u64 (read under a cut only), all zeroed
+  const size_t cells = (size_t)cnt * rounds * (size_t)groups;
+  const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
+  if ((rc = ensure(c, c->cgran, gbytes))) return rc;
+  HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
+  ba.cgran = static_cast<uint64_t*>(c->cgran.p);
+  ba.cpos = ba.cgran + cells;
+  ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
+  ba.nranks = 1;
+  ba.GT = groups;
+  ba.skip_release_at = -1;
+  ba.trace = nullptr;
+  if ((rc = timing_mark(cy, 0))) return rc;
+  const bool coop = fill_batch_args(c, ba, cy.kidx, groups, cy.per, i, cnt, cy.assume, cy.first_seq + i, cy.abort_word, false);
+  ++c->state_launches;
+  c->n_norm_pods += cnt;
+  cy.norm_pods += cnt;
+  if (kgpu::launch_nbatch(cy.dst, ba, groups, cy.kidx, c->spec, coop, c->stream))
+    return fail(c, KGPU_E_DEVICE, "k_nbatch launch failed");
+  cy.used_persistent = true;
+  return timing_close(cy, cnt);
+}
+
+// Pods [i, j), all with constant normalize maxima, in one persistent launch: k_cbatch under a cut, k_batch
+// otherwise (over the xGMI mailboxes on a node-sharded engine).
+int issue_batch_run(Cycle& cy, int32_t i, int32_t j) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  const int32_t cnt = j - i;
+  const int groups = cy.groups, kidx = cy.kidx;
+  const bool cut = cy.r.cut;
+  kgpu::BatchArgs ba{};
+  if (cut) {
+    // layout: granules [cnt][2][groups] u64 | position words [cnt] u64, all zeroed
+    const size_t cells = (size_t)cnt * 2 * (size_t)groups;
+    const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
+    if ((rc = ensure(c, c->cgran, gbytes))) return rc;
+    HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
+    ba.cgran = static_cast<uint64_t*>(c->cgran.p);
+    ba.cpos = ba.cgran + cells;
+    ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
+    ba.nranks = 1;
+    ba.GT = groups;
+  } else if (cy.r.xg) {
+    // every rank's mailbox ring (kgpu_xgmi_init); rows are addressed by the ring sequence
+    const size_t cells = (size_t)kgpu::kXgmiRing * (size_t)c->xg_GT;
+    ba.gran = static_cast<uint64_t*>(c->xg_box.p);
+    ba.feas = reinterpret_cast<int32_t*>(ba.gran + cells);
+    ba.pgran = static_cast<uint64_t* const*>(c->xg_arr.p);
+    ba.pfeas = reinterpret_cast<int32_t* const*>(static_cast<uint64_t* const*>(c->xg_arr.p) + c->xg_nranks);
+    ba.nranks = c->xg_nranks;
+    ba.rank = c->xg_rank;
+    ba.GT = c->xg_GT;
+    ba.R = kgpu::kXgmiRing;
+    ba.xseq0 = c->xg_seq;
+    c->xg_seq += cnt;
+  } else {
+    // layout: granules [cnt][groups] u64 | feasible counts [cnt][groups] i32; under early publish a slot
+    // holds both variants: two of each
+    ba.dual = c->batch_early && kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper) ? 1 : 0;
+    const size_t cells = (size_t)cnt * (size_t)groups * (ba.dual ? 2 : 1);
+    const size_t gbytes = sizeof(uint64_t) * cells + sizeof(int32_t) * cells;
+    if ((rc = ensure(c, c->gran, gbytes))) return rc;
+    HIP_OK(c, hipMemsetAsync(c->gran.p, 0, sizeof(uint64_t) * cells, c->stream));
+    ba.gran = static_cast<uint64_t*>(c->gran.p);
+    ba.feas = reinterpret_cast<int32_t*>(ba.gran + cells);
+    cy.run_ptrs.push_back({ba.gran, ba.feas});
+    void** slot = static_cast<void**>(c->batch_ptrs.p) + 2 * (cy.run_ptrs.size() - 1);
+    if ((rc = stage_h2d(c, slot, cy.run_ptrs.back().data(), sizeof(void*) * 2))) return rc;
+    ba.pgran = reinterpret_cast<uint64_t* const*>(slot);
+    ba.pfeas = reinterpret_cast<int32_t* const*>(slot + 1);
+    ba.nranks = 1;
+    ba.rank = 0;
+    ba.GT = groups;
+    ba.R = 0;
+  }
+  ba.skip_release_at = c->skip_release_at >= i && c->skip_release_at < i + cnt ? c->skip_release_at - i : -1;
+  ba.trace = nullptr;
+  if (c->phase_trace) {
+    if ((rc = ensure(c, c->trace, sizeof(int64_t) * 16 * (size_t)(cnt + 1)))) return rc;
+    HIP_OK(c, hipMemsetAsync(c->trace.p, 0, sizeof(int64_t) * 16 * (size_t)(cnt + 1), c->stream));
+    ba.trace = static_cast<int64_t*>(c->trace.p);
+    c->trace_host.assign((size_t)(cnt + 1) * 16, 0);
+  }
+  if ((rc = timing_mark(cy, 0))) return rc;
+  const bool coop = fill_batch_args(c, ba, kidx, groups, cy.per, i, cnt, cy.assume, cy.first_seq + i, cy.abort_word,
+                                    !cut && kgpu::batch_helper_used(c->spec, kidx, ba.R > 0, c->batch_helper));
+  ++c->state_launches;
+  if (cut) {
+    c->n_cut_pods += cnt;
+    cy.cut_pods += cnt;
+    if (kgpu::launch_cbatch(cy.dst, ba, groups, kidx, c->spec, coop, c->stream))
+      return fail(c, KGPU_E_DEVICE, "k_cbatch launch failed");
+  } else if (kgpu::launch_batch(cy.dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
+    return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
+  if ((rc = timing_close(cy, cnt))) return rc;
+  if (ba.trace)
+    HIP_OK(c, hipMemcpyAsync(c->trace_host.data(), ba.trace, sizeof(int64_t) * 16 * (size_t)(cnt + 1),
+                             hipMemcpyDeviceToHost, c->stream));
+  cy.used_persistent = true;
+  return KGPU_OK;
+}
+
+// Pods [i, j) one launch per pod; the next launch resolves (and assumes) the previous pod's winner.
+int issue_pod_chain(Cycle& cy, int32_t i, int32_t j) {
+  kgpu_ctx* c = cy.c;
+  const kgpu_route::CycleRoute& r = cy.r;
+  const bool one_pod = r.short_cycle && cy.n == 1;
+  int rc;
+  int prev = -1;
+  bool resolved_in_final = false;
+  for (int32_t k = i; k < j; ++k) {
+    const PodKind kind = cy.kinds[(size_t)k];
+    PodArgs a{};
+    a.pod = k;
+    a.prev = prev;
+    a.prev_blocks = cy.blocks;
+    a.prev_parity = (k - 1) & 1;
+    a.parity = k & 1;
+    // a one-pod diagnostic cycle of a pod without a normalize pass takes one launch: k_eval's last
+    // workgroup resolves it (resolve_tail) and writes the normalized rows k_final would
+    const bool one_launch = one_pod && cy.diag && !r.sharded && !r.cut && kind == PodKind::kConst;
+    // (a pod whose scoring fails keeps its normalize pass: its kind does not say whether it has one)
+    a.norm = (!one_launch && (cy.diag || r.cut || kind == PodKind::kNorm ||
+                              (kind == PodKind::kChain && needs_norm(c, cy.qs[k], cy.pools))))
+                 ? 1
+                 : 0;
+    a.assume = cy.assume;
+    a.diag = cy.diag ? 1 : 0;
+    a.zero_diag = r.zero_diag ? 1 : 0;
+    a.cut = r.cut ? 1 : 0;
+    a.seq = cy.first_seq + k;
+    // the chain's last pod with a normalize pass: k_final's last workgroup resolves it (k_eval's, for a
+    // one-launch cycle)
+    a.resolve_self = (k == j - 1 && (a.norm || one_launch) && !r.sharded) ? 1 : 0;
+    resolved_in_final = a.resolve_self != 0;
+    if (r.inline_q) {
+      a.q_inline = 1;
+      a.q = cy.qs[k];
+    }
+    // a one-pod diagnostic cycle ends on k_final's (k_eval's) resolving workgroup: it raises a pinned
+    // completion word once everything is written back, and the host returns on it
+    if (a.resolve_self && one_pod && !r.sharded && !c->timing && !c->phase_trace) {
+      int32_t* dw = reinterpret_cast<int32_t*>(static_cast<char*>(c->res_pin) + kCycDoneOff);
+      __atomic_store_n(dw, -1, __ATOMIC_RELEASE);
+      a.done_out = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->res_dev) + kCycDoneOff);
+      cy.done_word = dw;
+    }
+    if ((rc = zero_diag_rows(cy))) return rc;
+    ++c->state_launches;
+    if ((rc = timing_mark(cy, 0))) return rc;
+    if (cy.nom_dev && kgpu::launch_victims(cy.dst, cy.nom_dev, cy.st.N, c->stream))
+      return fail(c, KGPU_E_DEVICE, "k_victims launch failed");
+    if (kgpu::launch_eval(cy.dst, a, cy.blocks, cy.st.run_all ? 0 : c->spec, c->stream))  // run-all: the runtime profile
+      return fail(c, KGPU_E_DEVICE, "k_eval launch failed");
+    if (r.cut && kgpu::launch_cut(cy.dst, a, cy.blocks, c->cfg.n_filters, c->stream))
+      return fail(c, KGPU_E_DEVICE, "k_cut launch failed");
+    if ((rc = timing_close(cy, 1))) return rc;
+    if (r.sharded && a.norm && (rc = exchange(cy, a.parity, 1))) return rc;
+    if (a.norm && kgpu::launch_final(cy.dst, a, cy.blocks, cy.blocks, c->stream))
+      return fail(c, KGPU_E_DEVICE, "k_final launch failed");
+    if (r.sharded && (rc = exchange(cy, a.parity, 0))) return rc;
+    prev = k;
+  }
+  if (!resolved_in_final) {
+    PodArgs a{};
+    a.pod = -1;
+    a.prev = prev;
+    a.prev_blocks = cy.blocks;
+    a.prev_parity = prev & 1;
+    a.assume = cy.assume;
+    a.cut = r.cut ? 1 : 0;
+    if (kgpu::launch_resolve(cy.dst, cy.st.N, a, c->stream)) return fail(c, KGPU_E_DEVICE, "k_resolve launch failed");
+  }
+  return KGPU_OK;
+}
+
+// Every run of the call, in pod order.
+int issue_runs(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  int rc;
+  for (int32_t i = 0, j = 0; i < cy.n; i = j) {
+    const Route route = kgpu_route::route_of(cy.kinds[(size_t)i], cy.r);
+    if (route == Route::kTopo && cy.r.tbatch) {
+      if ((rc = issue_tbatch_run(cy, i, &j))) return rc;
+      if (j > i) continue;
     }
     if ((rc = arena_flush(c))) return rc;  // every other launch reads DevState / queries / pools from it
     c->tc.valid = false;                     // ... and may assume outside a persistent topology run
-    if (topo[(size_t)i]) {
-      ++c->state_launches;  // the per-pod topology pipeline
-      if ((rc = zero_diag_rows())) return rc;
-      const kgpu::QPlan& pl = plans[(size_t)i];
-      // the previous pod's resolve launch zeroes this pod's scratch only when it went through this
-      // pipeline too (a persistent topology run in between leaves it dirty)
-      if (scratch_zeroed_for != i)
-        HIP_OK(c, hipMemsetAsync(c->st.scratch, 0, sizeof(int64_t) * (size_t)pl.scratch_len, c->stream));
-      int64_t min_values = 0;
-      for (int k = 0; k < pl.n_hard; ++k)
-        if (pl.hard[k].key >= 0) min_values = std::max<int64_t>(min_values, c->key_n_values[pl.hard[k].key]);
-      const int64_t next = (i + 1 < n && topo[(size_t)i + 1]) ? plans[(size_t)i + 1].scratch_len : 0;
-      PodArgs a{};
-      a.pod = i;
-      a.prev = -1;
-      a.parity = i & 1;
-      a.norm = 1;
-      a.assume = assume;
-      a.diag = diag ? 1 : 0;
-      a.cut = cut ? 1 : 0;
-      a.seq = first_seq + i;
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
-      if (sharded) {
-        // Node-sharded topology pod: every rank builds the histograms of
-        // its shard; RCCL sums them (and ORs / mins / maxes the header) between the phases, so
-        // every rank filters and scores against the cluster-wide TpPairToMatchNum, topology
-        // scores, sizes and normalize extremes; the winner exchange is the non-topology one.
-        if (!c->comm) return fail(c, KGPU_E_STATE, "topology pods on a sharded engine need kgpu_comm_init");
-        int64_t* sc = c->st.scratch;
-        auto ar = [&](void* buf, size_t cnt, ncclDataType_t t, ncclRedOp_t op) -> int {
-          if (!cnt) return KGPU_OK;
-          const ncclResult_t r = rccl().AllReduce(buf, buf, cnt, t, op, c->comm, c->stream);
-          return r == ncclSuccess ? KGPU_OK : fail(c, KGPU_E_DEVICE, std::string("ncclAllReduce: ") + rccl().GetErrorString(r));
-        };
-        auto phase = [&](int ph, int64_t extra) -> int {
-          return kgpu::launch_topo_phase(dst, a, ph, blocks, extra, c->stream) ? fail(c, KGPU_E_DEVICE, "topology phase launch failed")
-                                                                                : KGPU_OK;
-        };
-        if ((rc = phase(0, 0)) || (rc = ar(sc, (size_t)pl.scratch_len, ncclInt64, ncclSum))) return rc;
-        if (min_values > 0 && (rc = phase(1, min_values))) return rc;
-        if ((rc = phase(2, 0))) return rc;
-        bool soft_sizes = false;
-        for (int k = 0; k < pl.n_soft; ++k) {
-          const kgpu::TSpread& t = pl.soft[k];
-          if (t.is_hostname || t.key < 0) continue;
-          if ((rc = ar(sc + pl.slot_off[t.rslot], (size_t)std::max(c->key_n_values[(size_t)t.key], 1), ncclInt64, ncclSum)))
-            return rc;
-          soft_sizes |= t.first_of_key != 0;
-        }
-        int32_t* h32 = reinterpret_cast<int32_t*>(sc);
-        const size_t i_feas = offsetof(kgpu::TopoHdr, feas_nonign) / 4, i_zones = offsetof(kgpu::TopoHdr, have_zones) / 4;
-        if (pl.n_soft && (rc = ar(h32 + i_feas, 1, ncclInt32, ncclSum))) return rc;
-        if (soft_sizes && (rc = phase(3, 0))) return rc;
-        if ((rc = phase(4, 0))) return rc;
-        // score extremes are max-encoded words (pts_min .. dpts_max), zone sums add, have_zones ORs
-        if ((rc = ar(sc + offsetof(kgpu::TopoHdr, pts_min) / 8, 5, ncclUint64, ncclMax)) ||
-            (rc = ar(h32 + i_zones, 1, ncclInt32, ncclMax)) ||
-            (rc = ar(sc + kgpu::kHdrWords, (size_t)std::max(c->st.n_zones, 0), ncclInt64, ncclSum)) ||
-            (rc = exchange(a.parity, 1)) || (rc = phase(5, blocks)) || (rc = exchange(a.parity, 0)) ||
-            (rc = phase(6, next)))
-          return rc;
-        scratch_zeroed_for = next > 0 ? i + 1 : -1;
-        if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-        ev += 2;
-        ++timed_passes;
-        i = i + 1;
-        continue;
-      }
-      if (c->topo_fused && !c->gbar.p) {
-        if ((rc = ensure(c, c->gbar, 64))) return rc;
-        HIP_OK(c, hipMemsetAsync(c->gbar.p, 0, 64, c->stream));
-        c->bar_base = 0;
-      }
-      if (kgpu::launch_topo(dst, a, blocks, min_values, next, c->topo_fused,
-                            static_cast<unsigned long long*>(c->gbar.p), c->bar_base, c->cfg.n_filters, c->stream,
-                            nom_dev, st.N))
-        return fail(c, KGPU_E_DEVICE, "topology pipeline launch failed");
-      if (c->topo_fused && !cut && !nom_dev) c->bar_base += (unsigned long long)kgpu::topo_barriers(min_values) * (unsigned long long)blocks;
-      scratch_zeroed_for = next > 0 ? i + 1 : -1;
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-      ev += 2;
-      ++timed_passes;
-      i = i + 1;
-      continue;
+    j = kgpu_route::segment_end(cy.kinds.data(), cy.n, i, cy.r);
+    rc = KGPU_OK;
+    switch (route) {
+      case Route::kTopo: rc = issue_topo_pod(cy, i); break;
+      case Route::kNBatch: rc = issue_nbatch_run(cy, i, j); break;
+      case Route::kBatch: rc = issue_batch_run(cy, i, j); break;
+      case Route::kChain: rc = issue_pod_chain(cy, i, j); break;
     }
-    if (!nrm.empty() && nrm[(size_t)i]) {
-      // a run that starts at a normalize-pass pod: one persistent launch of k_nbatch.  It extends over the
-      // following non-topology pods; a constant-maxima pod is absorbed (exact: its maxima come out 0) only
-      // while another normalize-pass pod lies within the next norm_persistent - 1 pods.  The granule area
-      // is capped at 64 MiB: a longer run continues in another launch (under a cut from cut_state).
-      const size_t rounds = cut ? 3 : 2;
-      const int32_t max_run = (int32_t)std::max<size_t>(1, ((size_t)64 << 20) / (8 * rounds * (size_t)groups + 8));
-      auto plain = [&](int32_t k) { return !topo[(size_t)k] && (nrm[(size_t)k] || !norm[(size_t)k]); };
-      while (j < n && j - i < max_run && plain(j)) {
-        if (!nrm[(size_t)j]) {
-          bool near = false;
-          for (int32_t k = j + 1; k < n && k - j < c->norm_persistent && plain(k) && !near; ++k) near = nrm[(size_t)k] != 0;
-          if (!near) break;
-        }
-        ++j;
-      }
-      const int32_t cnt = j - i;
-      kgpu::BatchArgs ba{};
-      // layout: granules [cnt][rounds][groups] u64 | position words [cnt] u64 (read under a cut only), all zeroed
-      const size_t cells = (size_t)cnt * rounds * (size_t)groups;
-      const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
-      if ((rc = ensure(c, c->cgran, gbytes))) return rc;
-      HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
-      ba.cgran = static_cast<uint64_t*>(c->cgran.p);
-      ba.cpos = ba.cgran + cells;
-      ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
-      ba.nranks = 1;
-      ba.GT = groups;
-      ba.first = i;
-      ba.count = cnt;
-      ba.per = per;
-      ba.assume = assume;
-      ba.seq0 = first_seq + i;
-      ba.abort = abort_word;
-      ba.abort_at = c->abort_at >= i && c->abort_at < i + cnt ? c->abort_at - i : -1;
-      ba.skip_release_at = -1;
-      ba.trace = nullptr;
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
-      const bool coop = c->coop || c->force_coop;
-      ba.hold = coop ? -1 : c->hold_group;
-      ++c->n_persist;
-      c->n_coop += coop ? 1 : 0;
-      ++c->state_launches;
-      note_geometry(c, 1, kidx, groups, per);
-      note_instantiation(c, kgpu::batch_row(c->spec), false, false, cnt);
-      c->n_norm_pods += cnt;
-      norm_pods += cnt;
-      if (kgpu::launch_nbatch(dst, ba, groups, kidx, c->spec, coop, c->stream))
-        return fail(c, KGPU_E_DEVICE, "k_nbatch launch failed");
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-      ev += 2;
-      timed_passes += cnt;
-      used_persistent = true;
-    } else if (kidx >= 0 && !norm[(size_t)i]) {
-      // a run of pods with constant normalize maxima: one persistent launch
-      // (a cut run's granule area is capped at 64 MiB: a longer run continues in another launch, which
-      // takes up the rotation from cut_state)
-      const int32_t max_run = cut ? (int32_t)std::max<size_t>(1, ((size_t)64 << 20) / (16 * (size_t)groups + 8)) : INT32_MAX;
-      while (j < n && !norm[(size_t)j] && !topo[(size_t)j] && (!xg || j - i < kgpu::kXgmiRing / 2) && j - i < max_run) ++j;
-      const int32_t cnt = j - i;
-      kgpu::BatchArgs ba{};
-      if (cut) {
-        // layout: granules [cnt][2][groups] u64 | position words [cnt] u64, all zeroed
-        const size_t cells = (size_t)cnt * 2 * (size_t)groups;
-        const size_t gbytes = (sizeof(uint64_t) * (cells + (size_t)cnt) + 15) & ~(size_t)15;
-        if ((rc = ensure(c, c->cgran, gbytes))) return rc;
-        HIP_OK(c, hipMemsetAsync(c->cgran.p, 0, gbytes, c->stream));
-        ba.cgran = static_cast<uint64_t*>(c->cgran.p);
-        ba.cpos = ba.cgran + cells;
-        ba.cut_nofilt = c->cfg.n_filters == 0 ? 1 : 0;
-        ba.nranks = 1;
-        ba.GT = groups;
-      } else if (xg) {
-        // every rank's mailbox ring (kgpu_xgmi_init); rows are addressed by the ring sequence
-        const size_t cells = (size_t)kgpu::kXgmiRing * (size_t)c->xg_GT;
-        ba.gran = static_cast<uint64_t*>(c->xg_box.p);
-        ba.feas = reinterpret_cast<int32_t*>(ba.gran + cells);
-        ba.pgran = static_cast<uint64_t* const*>(c->xg_arr.p);
-        ba.pfeas = reinterpret_cast<int32_t* const*>(static_cast<uint64_t* const*>(c->xg_arr.p) + c->xg_nranks);
-        ba.nranks = c->xg_nranks;
-        ba.rank = c->xg_rank;
-        ba.GT = c->xg_GT;
-        ba.R = kgpu::kXgmiRing;
-        ba.xseq0 = c->xg_seq;
-        c->xg_seq += cnt;
-      } else {
-        // layout: granules [cnt][groups] u64 | feasible counts [cnt][groups] i32; under early publish a slot
-        // holds both variants: two of each
-        ba.dual = c->batch_early && kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper) ? 1 : 0;
-        const size_t cells = (size_t)cnt * (size_t)groups * (ba.dual ? 2 : 1);
-        const size_t gbytes = sizeof(uint64_t) * cells + sizeof(int32_t) * cells;
-        if ((rc = ensure(c, c->gran, gbytes))) return rc;
-        HIP_OK(c, hipMemsetAsync(c->gran.p, 0, sizeof(uint64_t) * cells, c->stream));
-        ba.gran = static_cast<uint64_t*>(c->gran.p);
-        ba.feas = reinterpret_cast<int32_t*>(ba.gran + cells);
-        run_ptrs.push_back({ba.gran, ba.feas});
-        void** slot = static_cast<void**>(c->batch_ptrs.p) + 2 * (run_ptrs.size() - 1);
-        if ((rc = stage_h2d(c, slot, run_ptrs.back().data(), sizeof(void*) * 2))) return rc;
-        ba.pgran = reinterpret_cast<uint64_t* const*>(slot);
-        ba.pfeas = reinterpret_cast<int32_t* const*>(slot + 1);
-        ba.nranks = 1;
-        ba.rank = 0;
-        ba.GT = groups;
-        ba.R = 0;
-      }
-      ba.first = i;
-      ba.count = cnt;
-      ba.per = per;
-      ba.assume = assume;
-      ba.seq0 = first_seq + i;
-      ba.abort = abort_word;
-      ba.abort_at = c->abort_at >= i && c->abort_at < i + cnt ? c->abort_at - i : -1;
-      ba.skip_release_at = c->skip_release_at >= i && c->skip_release_at < i + cnt ? c->skip_release_at - i : -1;
-      ba.trace = nullptr;
-      if (c->phase_trace) {
-        if ((rc = ensure(c, c->trace, sizeof(int64_t) * 16 * (size_t)(cnt + 1)))) return rc;
-        HIP_OK(c, hipMemsetAsync(c->trace.p, 0, sizeof(int64_t) * 16 * (size_t)(cnt + 1), c->stream));
-        ba.trace = static_cast<int64_t*>(c->trace.p);
-        c->trace_host.assign((size_t)(cnt + 1) * 16, 0);
-      }
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
-      const bool coop = c->coop || c->force_coop;
-      ba.hold = coop ? -1 : c->hold_group;
-      ++c->n_persist;
-      c->n_coop += coop ? 1 : 0;
-      ++c->state_launches;
-      note_geometry(c, 1, kidx, groups, per);
-      note_instantiation(c, kgpu::batch_row(c->spec), ba.R > 0,
-                         !cut && kgpu::batch_helper_used(c->spec, kidx, ba.R > 0, c->batch_helper), cnt);
-      if (cut) {
-        c->n_cut_pods += cnt;
-        cut_pods += cnt;
-        if (kgpu::launch_cbatch(dst, ba, groups, kidx, c->spec, coop, c->stream))
-          return fail(c, KGPU_E_DEVICE, "k_cbatch launch failed");
-      } else if (kgpu::launch_batch(dst, ba, groups, kidx, c->spec, coop, c->batch_helper, c->stream))
-        return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
-      if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-      ev += 2;
-      timed_passes += cnt;
-      if (ba.trace)
-        HIP_OK(c, hipMemcpyAsync(c->trace_host.data(), ba.trace, sizeof(int64_t) * 16 * (size_t)(cnt + 1),
-                                 hipMemcpyDeviceToHost, c->stream));
-      used_persistent = true;
-    } else {
-      // one launch per pod; the next launch resolves (and assumes) the previous pod's winner
-      while (j < n && (kidx < 0 || norm[(size_t)j]) && !topo[(size_t)j] && (nrm.empty() || !nrm[(size_t)j])) ++j;
-      int prev = -1;
-      bool resolved_in_final = false;
-      for (int32_t k = i; k < j; ++k) {
-        PodArgs a{};
-        a.pod = k;
-        a.prev = prev;
-        a.prev_blocks = blocks;
-        a.prev_parity = (k - 1) & 1;
-        a.parity = k & 1;
-        // a one-pod diagnostic cycle of a pod without a normalize pass takes one launch: k_eval's last
-        // workgroup resolves it (resolve_tail) and writes the normalized rows k_final would
-        const bool one_launch = short_cycle && n == 1 && diag && !sharded && !cut &&
-                                !(qs[k].flags & KGPU_Q_SCORE_ERROR) && !needs_norm(c, qs[k], pools);
-        a.norm = (!one_launch && (diag || cut || needs_norm(c, qs[k], pools))) ? 1 : 0;
-        a.assume = assume;
-        a.diag = diag ? 1 : 0;
-        a.zero_diag = zero_diag ? 1 : 0;
-        a.cut = cut ? 1 : 0;
-        a.seq = first_seq + k;
-        // the chain's last pod with a normalize pass: k_final's last workgroup resolves it (k_eval's, for a
-        // one-launch cycle)
-        a.resolve_self = (k == j - 1 && (a.norm || one_launch) && !sharded) ? 1 : 0;
-        resolved_in_final = a.resolve_self != 0;
-        if (inline_q) {
-          a.q_inline = 1;
-          a.q = qs[k];
-        }
-        // a one-pod diagnostic cycle ends on k_final's (k_eval's) resolving workgroup: it raises a pinned
-        // completion word once everything is written back, and the host returns on it
-        if (a.resolve_self && short_cycle && n == 1 && !sharded && !c->timing && !c->phase_trace) {
-          int32_t* dw = reinterpret_cast<int32_t*>(static_cast<char*>(c->res_pin) + kCycDoneOff);
-          __atomic_store_n(dw, -1, __ATOMIC_RELEASE);
-          a.done_out = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->res_dev) + kCycDoneOff);
-          done_word = dw;
-        }
-        if ((rc = zero_diag_rows())) return rc;
-        ++c->state_launches;
-        if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev), c->stream));
-        if (nom_dev && kgpu::launch_victims(dst, nom_dev, st.N, c->stream))
-          return fail(c, KGPU_E_DEVICE, "k_victims launch failed");
-        if (kgpu::launch_eval(dst, a, blocks, st.run_all ? 0 : c->spec, c->stream))  // run-all: the runtime profile
-          return fail(c, KGPU_E_DEVICE, "k_eval launch failed");
-        if (cut && kgpu::launch_cut(dst, a, blocks, c->cfg.n_filters, c->stream))
-          return fail(c, KGPU_E_DEVICE, "k_cut launch failed");
-        if (c->timing) HIP_OK(c, hipEventRecord(get_event(c, ev + 1), c->stream));
-        ev += 2;
-        ++timed_passes;
-        if (sharded && a.norm && (rc = exchange(a.parity, 1))) return rc;
-        if (a.norm && kgpu::launch_final(dst, a, blocks, blocks, c->stream))
-          return fail(c, KGPU_E_DEVICE, "k_final launch failed");
-        if (sharded && (rc = exchange(a.parity, 0))) return rc;
-        prev = k;
-      }
-      if (!resolved_in_final) {
-        PodArgs r{};
-        r.pod = -1;
-        r.prev = prev;
-        r.prev_blocks = blocks;
-        r.prev_parity = prev & 1;
-        r.assume = assume;
-        r.cut = cut ? 1 : 0;
-        if (kgpu::launch_resolve(dst, st.N, r, c->stream)) return fail(c, KGPU_E_DEVICE, "k_resolve launch failed");
-      }
-    }
-    i = j;
+    if (rc) return rc;
   }
-  if (timed) HIP_OK(c, hipEventRecord(t1, c->stream));
+  return KGPU_OK;
+}
+
+// Read-backs, then the call's completion: the completion word of a one-pod cycle, or a synchronize.
+int await_cycle(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  const int32_t n = cy.n;
+  const bool short_cycle = cy.r.short_cycle;
+  int rc;
+  if (cy.timed) HIP_OK(c, hipEventRecord(cy.t1, c->stream));
   ht(c, 8);  // 8: launches issued (after run_tbatch's 5-7)
   // a long batch's records land in the pinned batch block (read back after the synchronize, before the
   // block can be reused)
-  kgpu_result* res_host = static_cast<kgpu_result*>(c->res_pin);
+  cy.res_host = static_cast<kgpu_result*>(c->res_pin);
   if (!short_cycle) {
     char* h = nullptr;
     if ((rc = c->batch_stage.reserve(stage_ops(c), sizeof(kgpu_result) * (size_t)n, 1 << 20, &h))) return rc;
-    res_host = reinterpret_cast<kgpu_result*>(h);
-    HIP_OK(c, hipMemcpyAsync(res_host, st.results, sizeof(kgpu_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    cy.res_host = reinterpret_cast<kgpu_result*>(h);
+    HIP_OK(c, hipMemcpyAsync(cy.res_host, cy.st.results, sizeof(kgpu_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     c->batch_stage.enqueued();
   }
-  if (used_persistent && !c->tb_abort_mapped)
-    HIP_OK(c, hipMemcpyAsync(&c->abort_host, abort_word, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  int32_t port_overflow = 0;
-  if (batch_ports) HIP_OK(c, hipMemcpyAsync(&port_overflow, c->st.port_overflow, 4, hipMemcpyDeviceToHost, c->stream));
+  if (cy.used_persistent && !c->tb_abort_mapped)
+    HIP_OK(c, hipMemcpyAsync(&c->abort_host, cy.abort_word, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (cy.batch_ports) HIP_OK(c, hipMemcpyAsync(&cy.port_overflow, c->st.port_overflow, 4, hipMemcpyDeviceToHost, c->stream));
   // A one-pod cycle whose last kernel raises a completion word, with no stream operation after it,
   // returns once the word lands (bounded: 2 s, then the synchronize below): the stream's own completion
   // signal reaches the host about 8 us later (profiles/r05_host_trace.txt).  The copies that fed the
   // kernel ran before it, so the staging blocks are free; settle() synchronizes before any operation
   // that is not ordered on the stream.
   bool landed = false;
-  if (done_word && short_cycle && n == 1 && !batch_ports && !timed && (!used_persistent || c->tb_abort_mapped)) {
+  if (cy.done_word && short_cycle && n == 1 && !cy.batch_ports && !cy.timed && (!cy.used_persistent || c->tb_abort_mapped)) {
     const int64_t t_end = now_ns() + 2000000000ll;
     const int32_t* ev = &static_cast<kgpu_result*>(c->res_pin)[0].evaluated;
     // a non-zero word is an abort code: the run wrote no record, so stop at once and let the
     // synchronize below complete the stream (an aborted cycle used to spin the full 2 s)
     for (;;) {
-      const int32_t w = __atomic_load_n(done_word, __ATOMIC_ACQUIRE);
+      const int32_t w = __atomic_load_n(cy.done_word, __ATOMIC_ACQUIRE);
       if (w > 0) break;
       if (w == 0 && __atomic_load_n(ev, __ATOMIC_ACQUIRE) != INT32_MIN) {
         landed = true;
@@ -2785,31 +2916,41 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     SYNC_OK(c);
   }
   ht(c, 9);  // 9: synchronize
-  std::memcpy(results, res_host, sizeof(kgpu_result) * (size_t)n);
-  if (used_persistent && c->tb_abort_mapped) {
+  std::memcpy(cy.results, cy.res_host, sizeof(kgpu_result) * (size_t)n);
+  return KGPU_OK;
+}
+
+// The completed call's outcome: abort word, port overflow, stats, the assumed pods' bookkeeping.
+int finish_cycle(Cycle& cy) {
+  kgpu_ctx* c = cy.c;
+  const int32_t n = cy.n;
+  const kgpu_pod_query* qs = cy.qs;
+  const kgpu_pools* pools = cy.pools;
+  const kgpu_result* results = cy.results;
+  if (cy.used_persistent && c->tb_abort_mapped) {
     // k_tbatch's last workgroup wrote the abort word (-1 left by the host: the run never finished)
     const int32_t w = __atomic_load_n(reinterpret_cast<int32_t*>(static_cast<char*>(c->res_pin) + kCycAbortOff),
                                       __ATOMIC_ACQUIRE);
     c->abort_host = w == -1 ? kgpu::kAbortDirty : w;
   }
-  if (used_persistent && c->abort_host == kgpu::kAbortClean && c->state_launches == 1 && !c->force_coop && !xg) {
+  if (cy.used_persistent && c->abort_host == kgpu::kAbortClean && c->state_launches == 1 && !c->force_coop && !cy.r.xg) {
     // A workgroup never started before the run resolved its first pod, and that run was the call's
     // only state-changing launch: nothing on the device changed.  The resident topology state's spare
     // buffer may be half zeroed: both buffers are recomputed from zeros by the next run.
     c->tc.valid = false;
     for (int k = 0; k < 2; ++k) c->tc.dirty[k] = c->tc.buf[k].bytes;
-    c->n_cut_pods -= cut_pods;
-    c->n_cut_topo_pods -= cut_topo_pods;
-    c->n_cut_topo_one -= cut_topo_one;
-    c->n_norm_pods -= norm_pods;
+    c->n_cut_pods -= cy.cut_pods;
+    c->n_cut_topo_pods -= cy.cut_topo_pods;
+    c->n_cut_topo_one -= cy.cut_topo_one;
+    c->n_norm_pods -= cy.norm_pods;
     return kCleanAbort;
   }
-  c->port_bound += batch_ports;
-  if (port_overflow) {
+  c->port_bound += cy.batch_ports;
+  if (cy.port_overflow) {
     c->uploaded = false;
     return fail(c, KGPU_E_DEVICE, "a node's host-port slots ran out during assume: re-upload the snapshot");
   }
-  if (used_persistent && c->abort_host) {
+  if (cy.used_persistent && c->abort_host) {
     // Pods resolved before the abort have already been assumed on the device, but their results
     // were never returned: the mirror no longer matches the caller's records.  Refuse further
     // cycles until the snapshot is uploaded again.
@@ -2817,67 +2958,64 @@ int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_
     return fail(c, KGPU_E_DEVICE, "persistent kernel gave up waiting for a workgroup (lost co-residency); the device "
                                   "mirror is invalid: re-upload the snapshot");
   }
-  if (stats) {
+  if (cy.stats) {
     float ms = 0.f;
-    HIP_OK(c, hipEventElapsedTime(&ms, t0, t1));
-    stats->pods += n;
-    stats->device_ms += ms;
-    int64_t placed = 0;
-    for (int32_t i = 0; i < n; ++i) placed += results[i].node >= 0;
-    stats->scheduled += placed;
-    if (c->timing) {
-      double sum = 0;
-      for (size_t e = 2; e < ev; e += 2) {
-        float k = 0.f;
-        HIP_OK(c, hipEventElapsedTime(&k, c->ev_pool[e], c->ev_pool[e + 1]));
-        sum += k;
-      }
-      stats->eval_kernel_ms += sum;
-      stats->eval_launches += timed_passes;
+    HIP_OK(c, hipEventElapsedTime(&ms, cy.t0, cy.t1));
+    double sum = 0;
+    for (size_t e = 2; c->timing && e < cy.ev; e += 2) {
+      float k = 0.f;
+      HIP_OK(c, hipEventElapsedTime(&k, c->ev_pool[e], c->ev_pool[e + 1]));
+      sum += k;
     }
+    add_stats(c, cy.stats, results, n, ms, sum, cy.timed_passes);
   }
-  if (assume && !c->nom.list.empty())
+  if (cy.assume && !c->nom.list.empty())
     for (int32_t i = 0; i < n; ++i)
       if (results[i].node >= 0) drop_nominated(c, qs[i].uid);
-  // keep host records of assumed pods for ForgetPod (and the pod table for later classes)
-  if (assume) {
+  if (cy.assume) {
     for (int32_t i = 0; i < n; ++i) {
       if (results[i].node < 0) continue;
-      {
-        kgpu_ctx::PodRow row;
-        row.node = results[i].node;
-        row.ns = qs[i].ns;
-        row.flags = query_pod_flags(qs[i]);
-        if (pools && qs[i].labels.count)
-          row.pairs.assign(pools->ints + qs[i].labels.begin, pools->ints + qs[i].labels.begin + qs[i].labels.count);
-        if (topo_on) {
-          const kgpu_range ot = plans[(size_t)i].own_tcls;
-          row.own_tcls.assign(aux.begin() + ot.begin, aux.begin() + ot.begin + ot.count);
-        }
-        c->pod_rows.push_back(std::move(row));
-      }
-      kgpu_ctx::PodRec a;
-      a.node = results[i].node;  // global: the row lives on this shard or on another rank's
-      a.q = qs[i];
-      a.active = true;
-      a.has_res = true;
-      if (pools) {
-        for (int k = 0; k < qs[i].scalars.count; ++k) a.sc.push_back(pools->scalars[qs[i].scalars.begin + k]);
-        for (int k = 0; k < qs[i].ports.count; ++k) a.ports.push_back(pools->ports[qs[i].ports.begin + k]);
-      }
-      c->recs.push_back(std::move(a));
+      const kgpu_pod_query& q = qs[i];
+      const kgpu_range ot = cy.sg.topo_on ? cy.sg.plans[(size_t)i].own_tcls : kgpu_range{0, 0};
+      record_assumed(c, q, results[i].node, pools && q.labels.count ? pools->ints + q.labels.begin : nullptr,
+                     pools && q.scalars.count > 0 ? pools->scalars + q.scalars.begin : nullptr,
+                     pools && q.ports.count > 0 ? pools->ports + q.ports.begin : nullptr,
+                     cy.sg.topo_on ? cy.sg.aux.data() + ot.begin : nullptr, ot.count);
     }
   }
-  c->last_diag = diag;
-  c->last_run_all = diag && c->run_all;
+  c->last_diag = cy.diag;
+  c->last_run_all = cy.diag && c->run_all;
   if (c->htrace) {
     ht(c, 10);  // 10: records, assumed-pod bookkeeping
     std::array<int64_t, kgpu_ctx::kHt> row{};
     std::copy(c->ht_cur, c->ht_cur + kgpu_ctx::kHt, row.begin());
-    (short_cycle ? c->ht_cycles : c->ht_batches).push_back(row);
-    c->ht_n += short_cycle ? 1 : 0;
+    (cy.r.short_cycle ? c->ht_cycles : c->ht_batches).push_back(row);
+    c->ht_n += cy.r.short_cycle ? 1 : 0;
   }
   return KGPU_OK;
+}
+
+int run_batch_once(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_pools* pools, int64_t first_seq,
+                   kgpu_result* results, kgpu_stats* stats, bool diag, int32_t assume) {
+  if (!c->uploaded) return fail(c, KGPU_E_STATE, "no snapshot uploaded");
+  if (n <= 0) return KGPU_OK;
+  int rc;
+  fail_point();
+  if (c->cut_fold && c->st.cut_state == nullptr && (rc = fold_rotation(c))) return rc;
+  const BatchCall call{qs, n, pools, first_seq, results, stats, diag, assume};
+  if (c->has_alias && !c->in_alias) return alias_cycles(c, call);
+  if (!c->nom.list.empty()) {
+    if (c->comm)
+      return fail(c, KGPU_E_UNSUPPORTED, "nominated pods on a node-sharded engine (the two-pass filter runs unsharded)");
+    if (n > 1) return nominated_cycles(c, call);
+  }
+  ArenaScope arena_scope{c};
+  Cycle cy(c, call);
+  if (n <= kShortCycle && (rc = begin_short_cycle(c, n))) return rc;
+  c->tb_abort_mapped = false;
+  ht(c, 0);
+  if ((rc = stage_cycle(cy)) || (rc = plan_routes(cy)) || (rc = issue_runs(cy)) || (rc = await_cycle(cy))) return rc;
+  return finish_cycle(cy);
 }
 
 // Per-node work buffers, the percentageOfNodesToScore cut and the math.Log table: everything
@@ -3538,16 +3676,12 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
       }
   }
   int per = 0, groups = 0;
-  const int kidx = kgpu::batch_geometry(c->st.N, std::min(c->max_groups > 0 ? std::min(c->max_groups, c->n_cus) : c->n_cus, 256),
-                                        &per, &groups, c->batch_geo_first);
+  const int kidx = kgpu::batch_geometry(c->st.N, persistent_groups(c), &per, &groups, c->batch_geo_first);
   if (kidx < 0) return fail(c, KGPU_E_UNSUPPORTED, "no persistent geometry for this node count");
   if (c->cut_fold && (rc = fold_rotation(c))) return rc;
   // the pools ride on the stream like every other copy (ordered after the batch in flight)
   if ((rc = upload_pools(c, pools))) return rc;
-  if (!c->ticket.p) {  // resolve_tail's counters: the top one and 8 group counters, a 64-byte line each
-    if ((rc = ensure(c, c->ticket, 9 * 64))) return rc;
-    HIP_OK(c, hipMemset(c->ticket.p, 0, 9 * 64));
-  }
+  if ((rc = ensure_ticket(c))) return rc;
   const int s = c->pipe_next;
   c->pipe_next ^= 1;
   kgpu_ctx::PipeSlot& ps = c->pipe[s];
@@ -3615,13 +3749,6 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   ba.GT = groups;
   ba.R = 0;
   ba.dual = dual ? 1 : 0;
-  ba.first = 0;
-  ba.count = n;
-  ba.per = per;
-  ba.assume = 1;
-  ba.seq0 = first_seq;
-  ba.abort = reinterpret_cast<int32_t*>(d + a_off);
-  ba.abort_at = -1;
   ba.skip_release_at = -1;
   ba.trace = nullptr;
   ba.res_out = static_cast<kgpu_result*>(ps.res_dev);
@@ -3630,15 +3757,12 @@ int pipe_submit(kgpu_ctx* c, const kgpu_pod_query* qs, int32_t n, const kgpu_poo
   kgpu_ctx::PipeSlot& po = c->pipe[s ^ 1];
   ba.zero_buf = static_cast<uint64_t*>(po.gran.p);
   ba.zero_n16 = po.gran.p ? (int64_t)(po.gran.bytes / 16) : 0;
-  const bool coop = c->coop;
-  ba.hold = -1;
-  ++c->n_persist;
-  c->n_coop += coop ? 1 : 0;
   *reinterpret_cast<int32_t*>(static_cast<char*>(ps.res) + sizeof(kgpu_result) * (size_t)n) = -1;
   const bool timed = stats != nullptr;
   if (timed) HIP_OK(c, hipEventRecord(ps.t0, c->stream));
-  note_geometry(c, 1, kidx, groups, per);
-  note_instantiation(c, kgpu::batch_row(c->spec), false, kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper), n);
+  // (no abort_at, no hold, no forced cooperative launch here: pipe_eligible and run_batch see to that)
+  const bool coop = fill_batch_args(c, ba, kidx, groups, per, 0, n, 1, first_seq, reinterpret_cast<int32_t*>(d + a_off),
+                                    kgpu::batch_helper_used(c->spec, kidx, false, c->batch_helper));
   if (kgpu::launch_batch(reinterpret_cast<const DevState*>(d), ba, groups, kidx, c->spec, coop, c->batch_helper,
                          c->stream))
     return fail(c, KGPU_E_DEVICE, "k_batch launch failed");
@@ -3684,34 +3808,16 @@ int pipe_finish(kgpu_ctx* c, kgpu_ctx::PipeBatch& b) {
   if (b.stats) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ps.t0, ps.t1) != hipSuccess) ms = 0.f;
-    b.stats->pods += b.n;
-    b.stats->device_ms += ms;
-    int64_t placed = 0;
-    for (int32_t i = 0; i < b.n; ++i) placed += b.results[i].node >= 0;
-    b.stats->scheduled += placed;
-    if (c->timing) {
-      b.stats->eval_kernel_ms += ms;
-      b.stats->eval_launches += b.n;
-    }
+    add_stats(c, b.stats, b.results, b.n, ms, ms, b.n);
   }
   for (int32_t i = 0; i < b.n; ++i) {
     if (b.results[i].node < 0) continue;
     const kgpu_pod_query& q = b.qs[(size_t)i];
-    kgpu_ctx::PodRow row;
-    row.node = b.results[i].node;
-    row.ns = q.ns;
-    row.flags = query_pod_flags(q);
-    if (q.labels.count && q.labels.begin + q.labels.count <= (int32_t)b.ints.size())
-      row.pairs.assign(b.ints.begin() + q.labels.begin, b.ints.begin() + q.labels.begin + q.labels.count);
-    c->pod_rows.push_back(std::move(row));
-    kgpu_ctx::PodRec a;
-    a.node = b.results[i].node;
-    a.q = q;
-    a.active = true;
-    a.has_res = true;
-    if (q.scalars.count && q.scalars.begin + q.scalars.count <= (int32_t)b.scalars.size())
-      a.sc.assign(b.scalars.begin() + q.scalars.begin, b.scalars.begin() + q.scalars.begin + q.scalars.count);
-    c->recs.push_back(std::move(a));
+    // the saved pool copies are the caller's at submit: a range outside them is dropped
+    const bool pairs_ok = q.labels.count && q.labels.begin + q.labels.count <= (int32_t)b.ints.size();
+    const bool sc_ok = q.scalars.count && q.scalars.begin + q.scalars.count <= (int32_t)b.scalars.size();
+    record_assumed(c, q, b.results[i].node, pairs_ok ? b.ints.data() + q.labels.begin : nullptr,
+                   sc_ok ? b.scalars.data() + q.scalars.begin : nullptr, nullptr, nullptr, 0);
   }
   c->last_diag = false;
   return KGPU_OK;
